@@ -13,7 +13,7 @@ fused into the norm launch that consumes it; `collective_transport` in the outpu
 or -- CHITU_ALLREDUCE=rccl, or when the xGMI self-test fails -- through RCCL with the step replayed as
 hipGraph pieces between the library calls (chitu_amd/graphs.py).  At N=8 this IS the metric's configuration.
 
-`python bench.py --gpus N` with N > 1 and no launcher environment re-executes itself under
+`python bench.py --gpus N` with N > 1 and no launcher environment runs itself again in a child process under
 `torch.distributed.run` (one rank per GPU; when the box has fewer than N GPUs every rank shares cuda:0,
 the process group is gloo, the layer count is cut to what fits, and the line is flagged invalid: a
 functional check of the N > 1 code path, not a measurement).
@@ -46,6 +46,14 @@ must equal them bit for bit -- per measured loop in `replay_vs_eager_after_timin
 `captures_rejected_and_repeated` echo chitu_amd.graphs.capture_verified's log (every capture is checked by one replay
 before it is used).  Anything but equality voids the line (`invalid`, `value` null).  `cpu_baseline.reference_fields`
 says which of its fields are static records (the reference's own CPU decode cannot be timed on the GPU box: no reference tree).
+
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline figure needs: it builds the model,
+runs W warm-up steps, times K steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` and the graph check above; every other figure is null or absent).  Everything else described above -- bs 1 /
+32, the rocm-smi replica loop, `collectives.per_transport`, `step_*` and `roofline`, `box_calibration`, the extra models,
+`prefill`, `cpu_baseline` -- runs only with `--full` (each part can still be switched off there by its `--no-*` option).
+`--dump-outputs DIR` writes what the last timed step returned -- the fp32 logits and the greedy next tokens -- as
+DIR/<name>.npy; with the same arguments the inputs are the same from run to run.
 
 Prints ONE JSON line on rank 0.
 """
@@ -95,11 +103,19 @@ def parse():
     ap.add_argument("--no-calibration", action="store_true",
                     help="kernel-trace tools only: skip box_calibration (its probes' launches would sit in the trace)")
     ap.add_argument("--no-llama", action="store_true", help="skip the extra Llama-3-8B / DeepSeek-V2-Lite / Mixtral-int8 (BASELINE configs 2, 3, 4) measurements")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure (bs 1 / 32, device state, collectives per transport, "
+                         "roofline, box calibration, the extra models and prefill, CPU baseline); the --no-* options apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (fp32 logits, next tokens) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def self_launch(n):
-    """`python bench.py --gpus N` without a launcher: become `torch.distributed.run` with N ranks."""
+    """`python bench.py --gpus N` without a launcher: run `torch.distributed.run` with N ranks as a child, exit with its status."""
     import socket
 
     sock = socket.socket()
@@ -111,7 +127,9 @@ def self_launch(n):
         env["CHITU_BENCH_BACKEND"] = "gloo"  # every rank on cuda:0: functional check only
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execvpe(sys.executable, cmd, env)
+    import subprocess
+
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def setup_dist(n):
@@ -520,8 +538,9 @@ def build_model(args_ns, rank):
     return margs, model, cache
 
 
-def run_decode(model, cache, reqs, tokens, steps, world, use_graph, timed):
-    """Exactly `steps` decode steps; returns (seconds (max over ranks) or None, final tokens)."""
+def run_decode(model, cache, reqs, tokens, steps, world, use_graph, timed, last=None):
+    """Exactly `steps` decode steps; returns (seconds (max over ranks) or None, final tokens).  `last` (a dict): filled, after
+    the clock has stopped, with the logits and next tokens the last step returned."""
     from chitu_amd import sampling
 
     if timed:
@@ -538,6 +557,8 @@ def run_decode(model, cache, reqs, tokens, steps, world, use_graph, timed):
         return None, tokens
     barrier_sync(world)
     dt = time.perf_counter() - t0
+    if last is not None and steps > 0:  # the graph's output buffer is overwritten by the next step: copy it now
+        last["logits"], last["next_tokens"] = logits.clone(), tokens.clone()
     if world > 1:
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -562,18 +583,43 @@ def check_graph_against_eager(model, cache, reqs, tokens, use_graph, tag):
     GRAPH_CHECKS[tag] = bool(torch.equal(eager, replay))
 
 
-def measure(model, cache, bs, ctx, steps, warmup, world, use_graph, tag):
+def measure(model, cache, bs, ctx, steps, warmup, world, use_graph, tag, last=None):
     reqs = [f"{tag}{i}" for i in range(bs)]
     for r in reqs:
         cache.register_sequence(r, ctx)
     gen = torch.Generator(device="cuda").manual_seed(5)
     tokens = torch.randint(100, 1000, (bs,), device="cuda", generator=gen)
     _, tokens = run_decode(model, cache, reqs, tokens, warmup, world, use_graph, timed=False)
-    dt, tokens = run_decode(model, cache, reqs, tokens, steps, world, use_graph, timed=True)
+    dt, tokens = run_decode(model, cache, reqs, tokens, steps, world, use_graph, timed=True, last=last)
     check_graph_against_eager(model, cache, reqs, tokens, use_graph, tag)
     for r in reqs:
         cache.finalize_cache_all_decode(r)
     return dt
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as `out_dir/<name>.npy`, float32 (integers as float64, exact).  An array larger than its
+    share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample of its flattened elements (sorted indices, the same for
+    every run of the same shapes) with the indices beside it as `<name>_sample_index.npy`."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        a = t.to(torch.float64 if not t.is_floating_point() else torch.float32).numpy()
+        if a.size * a.itemsize > share:
+            n = share // (a.itemsize + 8)  # each sampled element also costs its float64 index
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=n, replace=False))
+            np.save(os.path.join(out_dir, f"{name}_sample_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def roofline_array(roof):
@@ -1293,16 +1339,23 @@ def main():
         if ok.item() == 0:
             use_graph, graph_mode = False, "off (full capture refused)"
             model.graphs, model.static_tokens, model.static_out, model.graph_pool = {}, {}, {}, None
-    dt = measure(model, cache, a.bs, a.ctx, a.steps, a.warmup, world, use_graph, "m")
+    last = {}
+    dt = measure(model, cache, a.bs, a.ctx, a.steps, a.warmup, world, use_graph, "m", last=last)
     ms_per_step = dt / a.steps * 1e3
-    # the same loop once more, NOT part of any reported time, with rocm-smi sampled beside it
-    with DeviceStateSampler(local if not dinfo["shared_device"] else 0) as dev_state:
-        measure(model, cache, a.bs, a.ctx, max(a.steps, 96), 0, world, use_graph, "d")
+    if a.dump_outputs and rank == 0:
+        dumped = dump_outputs(a.dump_outputs, last)
+        print(f"[bench] last timed step's outputs written to {a.dump_outputs}: {dumped}", file=sys.stderr)
+    del last
+    dev_state = None
+    if a.full:
+        # the same loop once more, NOT part of any reported time, with rocm-smi sampled beside it
+        with DeviceStateSampler(local if not dinfo["shared_device"] else 0) as dev_state:
+            measure(model, cache, a.bs, a.ctx, max(a.steps, 96), 0, world, use_graph, "d")
     node_tok_s = a.bs * a.steps / dt
     value = node_tok_s * world / SHARD
 
     extra = {}
-    for b in batches[1:]:  # BASELINE config 5: bs in {1, 16, 32}
+    for b in batches[1:] if a.full else ():  # BASELINE config 5: bs in {1, 16, 32}
         dtb = measure(model, cache, b, a.ctx, a.steps, a.warmup, world, use_graph, f"s{b}_")
         extra[f"bs{b}"] = {
             "ms_per_step": round(dtb / a.steps * 1e3, 4), "node_tok_s": round(b * a.steps / dtb, 2),
@@ -1315,7 +1368,7 @@ def main():
                 "ranks_seen_by_library": dinfo["ranks_seen"],
                 "fused": "every per-layer all-reduce runs inside the launch that also does the top-k sum, the residual "
                          "add, the RMSNorm and the fp8 quant" if transport.startswith("xgmi") else "no"}
-        timing = time_collectives(a.bs, margs.dim, model.vocab_local)
+        timing = time_collectives(a.bs, margs.dim, model.vocab_local) if a.full else {}
         coll.update(timing)
         if timing.get("allreduce_add_norm_quant_us") and timing.get("logits_all_gather_us"):
             coll["collective_ms_per_step_est"] = round(
@@ -1336,7 +1389,7 @@ def main():
                 "note": "one rank of eight: the 124 collectives of the TP=8 step are not paid here"}
 
     roof = None
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # the routing capture runs decode steps, i.e. collectives at N > 1: every rank takes part;
         # the kernel timing itself is rank 0's
         routing = capture_step_routing(model, cache, a.bs, a.ctx)
@@ -1345,7 +1398,7 @@ def main():
         if world > 1:
             dist.barrier()
     calib = None
-    if rank == 0 and not a.no_calibration:
+    if a.full and rank == 0 and not a.no_calibration:
         w2_us = None
         for k in (roofline_array(roof) or []):
             if "gemm2" in str(k.get("kernel", "")):
@@ -1362,9 +1415,11 @@ def main():
         calib["static_device_facts"] = static_device_facts(local if not dinfo["shared_device"] else 0)
     if world > 1:
         dist.barrier()
-    distinct = (roof["distinct_experts"] - 1) if roof else min(256, a.bs * 8)  # routed only; shared counted in the formula
-    step_bytes = algorithmic_bytes_per_step(margs, a.bs, a.ctx, distinct)
-    if world == 1 and not a.no_llama and a.layers == 61:
+    step_bytes = None  # a roofline figure: --full only
+    if a.full:
+        distinct = (roof["distinct_experts"] - 1) if roof else min(256, a.bs * 8)  # routed only; shared counted in the formula
+        step_bytes = algorithmic_bytes_per_step(margs, a.bs, a.ctx, distinct)
+    if a.full and world == 1 and not a.no_llama and a.layers == 61:
         del model, cache
         model = cache = None
         torch.cuda.empty_cache()
@@ -1374,7 +1429,7 @@ def main():
         extra["ep8_rank"] = ep8_rank_extra(a.steps, a.warmup, a.ctx)
         extra["prefill"] = prefill_extra()
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         model = cache = None
         torch.cuda.empty_cache()
         cpu = cpu_baseline(margs, a.bs, a.ctx)
@@ -1403,12 +1458,12 @@ def main():
             "value_normalised_is": "value x box_calibration.step_time_factor: what the reference box of the calibration constants "
                                    "would be expected to measure (two-term model; the measured `value` stands)",
             "collectives": coll,
-            "step_algorithmic_GB": round(step_bytes / 1e9, 3),
-            "step_hbm_GBs": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1),
-            "step_roofline_frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+            "step_algorithmic_GB": round(step_bytes / 1e9, 3) if step_bytes else None,
+            "step_hbm_GBs": round(step_bytes / (ms_per_step * 1e-3) / 1e9, 1) if step_bytes else None,
+            "step_roofline_frac": round(step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if step_bytes else None,
             "roofline": roof, "roofline_kernels": roofline_array(roof), "cpu_baseline": cpu, "build_s": round(build_s, 1),
             "graph_verified": graph_rep,
-            "device_state_under_load": dev_state.summary(),
+            "device_state_under_load": dev_state.summary() if dev_state else None,
         }
         res.update(extra)
         if a.opt:

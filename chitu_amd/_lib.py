@@ -28,7 +28,9 @@ class HipCallError(RuntimeError):
 
 def build(verbose: bool = False) -> str:
     """Compile every .hip under csrc/ for gfx950 and link libchitu_hip.so (in-tree)."""
-    cmd = ["make", "-C", CSRC_DIR, "-j", str(os.cpu_count() or 4)]
+    # MAX_JOBS if set, else at most 16 jobs: on a shared host os.cpu_count() is the whole machine, not this build's share
+    jobs = os.environ.get("MAX_JOBS") or str(min(16, os.cpu_count() or 4))
+    cmd = ["make", "-C", CSRC_DIR, "-j", jobs]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout)

@@ -15,6 +15,8 @@ BLOCK = 128
 # GPU (PTX cvt.rn) and what gfx950 does.  tests/test_oracle_golden.py swaps in the Triton
 # *interpreter's* casts (round-half-up without exponent carry for fp8, truncation for bf16) to
 # pin these restatements bit-exactly against fixtures generated under TRITON_INTERPRET=1.
+# "matmul" (the oracles' fp32 matmuls, here and in mla.py) defaults to the host BLAS; the same test swaps in the summation
+# order of the BLAS its CPU-run fixtures were made with, so that they pin bit for bit on any host.
 def _to_fp8_rne(t: torch.Tensor) -> torch.Tensor:
     return t.to(torch.float8_e4m3fn)
 
@@ -23,7 +25,7 @@ def _to_out_rne(t: torch.Tensor, dtype) -> torch.Tensor:
     return t.to(dtype)
 
 
-CAST = {"fp8": _to_fp8_rne, "out": _to_out_rne}
+CAST = {"fp8": _to_fp8_rne, "out": _to_out_rne, "matmul": torch.matmul}
 
 
 def to_fp8(t):
@@ -93,7 +95,7 @@ def fp8_gemm_deepseek_v3(a_q, a_s, b_q, b_s, out_dtype=torch.bfloat16):
     bs_rows = b_s.repeat_interleave(BLOCK, dim=0)[:N]  # [N, K/128]
     for kb in range(K // BLOCK):
         sl = slice(kb * BLOCK, (kb + 1) * BLOCK)
-        dot = a[:, sl] @ b[:, sl].T
+        dot = CAST["matmul"](a[:, sl], b[:, sl].T)
         acc += dot * a_s[:, kb : kb + 1] * bs_rows[:, kb][None, :]
     return to_out(acc, out_dtype).reshape(*a_q.shape[:-1], N)
 

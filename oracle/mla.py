@@ -8,6 +8,8 @@ The split-KV / LSE merge of the reference is mathematically the identity on this
 
 import torch
 
+from .fp8 import CAST
+
 
 def gather_pages(cache, block_table_row, length):
     """cache [P, page, D] -> [length, D] following the block table (attn_backend.py:716-760)."""
@@ -29,9 +31,9 @@ def mla_decode(q_nope, q_pe, cache, block_table, seqlens, scale, kv_lora_rank=51
             continue
         kv = gather_pages(cache, block_table[b], L).float()
         c, pe = kv[:, :kv_lora_rank], kv[:, kv_lora_rank:]
-        s = (q_nope[b].float() @ c.T + q_pe[b].float() @ pe.T) * scale
+        s = (CAST["matmul"](q_nope[b].float(), c.T) + CAST["matmul"](q_pe[b].float(), pe.T)) * scale
         p = torch.softmax(s, dim=-1)
-        out[b] = p @ c
+        out[b] = CAST["matmul"](p, c)
     return out
 
 

@@ -2,6 +2,7 @@
 (tests/golden/gen_golden.py, Triton interpreter) and its documented known-answer vector."""
 
 import ctypes
+import json
 import os
 
 import numpy as np
@@ -282,9 +283,11 @@ def test_gqa_prefill_oracle_matches_reference_varlen_attention():
 
 def _ref_model_setup():
     from chitu_amd.deepseek_v3 import DeepSeekV3Args, compute_softmax_scale, precompute_freqs_cis
-    from tests.golden.gen_ref_model import PROMPTS, TINY
     from tests.util import ref_model_case
 
+    with open(os.path.join(ROOT, "tests", "golden", "ref_model_v3.json")) as f:  # what gen_ref_model.py ran the reference on
+        setup = json.load(f)
+    TINY, PROMPTS = setup["tiny"], setup["prompts"]
     g, params = ref_model_case()
     keys = ("vocab_size", "dim", "inter_dim", "moe_inter_dim", "n_layers", "n_dense_layers", "n_heads", "n_routed_experts",
             "n_shared_experts", "n_activated_experts", "n_expert_groups", "n_limited_groups", "route_scale", "score_func",
@@ -364,14 +367,37 @@ def _oracle_decode_model(params, cfg, n_layers, n_dense, prompts, fed, cos_t, si
     return out, {k: (e, float(np.mean(m))) for k, (e, m) in stats.items()}
 
 
-def test_decode_layers_bit_exact_vs_the_reference_models_own_run(interpreter_casts):
+def _fixture_host_matmul(a, b, k_block=256):
+    """fp32 a @ b summed in the order of the BLAS the CPU-run reference fixtures were made with (oneMKL's AVX-512 sgemm at
+    these shapes, matched bit for bit there): K in blocks of 256, each block one fused multiply-add chain from zero in k
+    order, the block results added in order.  The fp32 products are exact in fp64, so fp64 add + one rounding to fp32 is
+    the FMA's single rounding (but for double-rounding ties); every step is an elementwise IEEE op, alike on every host."""
+    a64, b64 = a.double(), b.double()
+    out = None
+    for k0 in range(0, a.shape[-1], k_block):
+        acc = torch.zeros(a.shape[0], b.shape[1], dtype=torch.float32)
+        for k in range(k0, min(a.shape[-1], k0 + k_block)):
+            acc = (acc.double() + a64[:, k, None] * b64[None, k, :]).float()
+        out = acc if out is None else out + acc
+    return out
+
+
+@pytest.fixture
+def fixture_blas_order(monkeypatch):
+    """The oracles' fp32 matmuls in the fixture host's summation order instead of this host's BLAS (another code path
+    rounds the attention's sums differently, which the pin below would see)."""
+    monkeypatch.setitem(ofp8.CAST, "matmul", _fixture_host_matmul)
+
+
+def test_decode_layers_bit_exact_vs_the_reference_models_own_run(interpreter_casts, fixture_blas_order):
     """oracle/deepseek.py (rms_norm + attention_decode + mlp + gate + MoE + residuals) against the reference's OWN
     TransformerDeepSeekV3 run on CPU (tests/golden/gen_ref_model.py: prefill of two ragged prompts + two decode steps;
     every FP8 linear and the RoPE are the reference's Triton kernels under the interpreter, whose cast defects the
     fixture `interpreter_casts` emulates; the MoE is the reference's per-expert loop = oracle moe_layer_loop).
     Every sublayer gets the reference's own input for that token (prefill is replayed token by token through the
     decode path) and must reproduce the reference's output bit for bit, up to the fp32 summation order of the
-    attention over several keys (one bf16 flip seen; bounded below)."""
+    attention over several keys (one bf16 flip seen; bounded below).  The fp32 matmuls follow the fixture host's BLAS
+    order (`fixture_blas_order`), so the pin holds on any host."""
     g, params, cfg, prompts, cos_t, sin_t = _ref_model_setup()
     out, stats = _oracle_decode_model(params, cfg, 3, 1, prompts, g["fed"], cos_t, sin_t, ref=g)
     for k, (err, mism) in stats.items():

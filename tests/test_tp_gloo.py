@@ -43,6 +43,9 @@ def _run(fn, world, *args):
 
 def _entry(fn, rank, world, port, q, *args):
     try:
+        # CPU ranks on any host: the device stays hidden from them (before HIP initialises), so a host with a GPU runs what a
+        # host without one does -- including the no-device verdict of the transport decision in _tp_layers
+        os.environ["HIP_VISIBLE_DEVICES"] = "-1"
         os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
         torch.set_num_threads(2)
         dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -5,6 +5,7 @@
 # --kernel-trace --pmc only (no sys/hip/memory tracing next to counters).  The step runs EAGERLY (--no-graph) on a
 # few layers so every dispatch is attributed to its kernel; tools/pmc_report.py turns the .db files into
 # profiles/r02_pmc_step.json.
+repo=$(cd "$(dirname "$0")/.." && pwd)  # this script lives in tools/
 out=$1; shift
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
@@ -15,7 +16,7 @@ for grp in "FETCH_SIZE" "WRITE_SIZE" "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GR
            "SQ_INSTS_VALU_MFMA_MOPS_F8 SQ_INSTS_VALU_MFMA_MOPS_BF16 SQ_INSTS_MFMA SQ_INSTS_VALU"; do
   tag=$(echo "$grp" | tr ' ' '+' | cut -c1-40)
   rm -rf "/tmp/pmc_$tag"
-  timeout 300 rocprofv3 --kernel-trace --pmc $grp -d "/tmp/pmc_$tag" -o pmc -- python "$GRAFT_REPO_ROOT/bench.py" $args > "$out/pmc_$tag.log" 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $grp -d "/tmp/pmc_$tag" -o pmc -- python "$repo/bench.py" --full $args > "$out/pmc_$tag.log" 2>&1
   db=$(ls /tmp/pmc_$tag/*.db /tmp/pmc_$tag/*/*.db 2>/dev/null | head -1)
   if [ -n "$db" ]; then
     python "$GRAFT_REPO_ROOT/tools/pmc_summary.py" "$db" chitu:: > "$out/pmc_$tag.json" 2>> "$out/pmc_$tag.log"

@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 out=$GRAFT_REPO_ROOT/gpurun_out/r06_n2_bisect; mkdir -p $out
 run() {  # name dir env...
   name=$1; dir=$2; shift 2
-  ( cd $dir && env "$@" timeout 500 python bench.py --gpus 2 --layers 12 --steps 8 --warmup 2 --no-llama --no-cpu-baseline --no-roofline > $out/$name.json 2> $out/$name.err; echo "$name rc=$?" )
+  ( cd $dir && env "$@" timeout 500 python bench.py --full --gpus 2 --layers 12 --steps 8 --warmup 2 --no-llama --no-cpu-baseline --no-roofline > $out/$name.json 2> $out/$name.err; echo "$name rc=$?" )
   grep -h "failed its replay check\|does not reproduce" $out/$name.err | sort | uniq -c | cut -c1-260
 }
 run r05tree $GRAFT_REPO_ROOT/gpurun_stage/r05tree A=1

@@ -12,11 +12,11 @@ for lib in "" $NOSLP; do
     CHITU_HIP_LIB=$lib HUNT_POISON=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 2970$i tools/r06_race_hunt.py 32 12 30 0 2>&1 | grep "repetitions differ" >> $out/hunt_$tag.txt
   done
   echo "== hunt $tag"; cat $out/hunt_$tag.txt
-  CHITU_HIP_LIB=$lib timeout 500 python bench.py --gpus 2 --layers 12 --steps 8 --warmup 2 --no-llama --no-cpu-baseline --no-roofline > $out/n2_$tag.json 2> $out/n2_$tag.err; echo "n2 $tag rc=$?"
+  CHITU_HIP_LIB=$lib timeout 500 python bench.py --full --gpus 2 --layers 12 --steps 8 --warmup 2 --no-llama --no-cpu-baseline --no-roofline > $out/n2_$tag.json 2> $out/n2_$tag.err; echo "n2 $tag rc=$?"
   grep -h "failed its replay check\|does not reproduce" $out/n2_$tag.err | sort | uniq -c | cut -c1-200
 done
 for rep in 1 2; do for lib in "" $NOSLP; do
-  CHITU_HIP_LIB=$lib python bench.py --no-cpu-baseline --no-roofline --no-llama | python -c "
+  CHITU_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-roofline --no-llama | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('${lib:-in-tree}', d['ms_per_step'], d.get('bs1',{}).get('ms_per_step'), d.get('bs32',{}).get('ms_per_step'))"
   CHITU_HIP_LIB=$lib timeout 300 python tools/prefill_bench.py 8 2048 2>/dev/null | grep prompt_tokens
 done; done 2>&1 | grep -v amdgpu.ids | tee $out/ab_step.txt

@@ -6,17 +6,18 @@
 # Writes gpurun_out/<tag>/: the bench line, step breakdowns (bs 16 / 1 / 32) + whole-process kernel traces, the PMC
 # passes (tools/pmc_passes.sh -> pmc_step.json, what bench.py reads as profiles/r03_pmc_step.json), Llama bs-1 trace,
 # prefill timings + trace, bs sweep.  ~2 GPU-minutes of run time on a warm box (r03: 96-108 s).  Copy what is to be judged into profiles/.
+repo=$(cd "$(dirname "$0")/.." && pwd)  # this script lives in tools/
 tag=${1:-sweep}
 head=${2:-unknown}
 out=$GRAFT_REPO_ROOT/gpurun_out/$tag
 mkdir -p $out
 echo "$head" > $out/git_head.txt
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python $GRAFT_REPO_ROOT/bench.py > $out/bench.json 2> $out/bench_err.txt
+timeout 600 python "$repo/bench.py" --full > $out/bench.json 2> $out/bench_err.txt
 # QUICK=1: the bench line, the bs 16 / bs 1 traces, the PMC passes and the 2048-token prefill trace only (a late-round refresh)
 for bs in 16 1 $([ -z "${QUICK:-}" ] && echo 32); do
   rm -rf /tmp/pb$bs
-  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/pb$bs -o t -- python $GRAFT_REPO_ROOT/bench.py --bs $bs --steps 8 --warmup 2 --no-bs1 --no-llama --no-cpu-baseline --no-calibration --no-graph-check > /tmp/pb$bs.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/pb$bs -o t -- python "$repo/bench.py" --full --bs $bs --steps 8 --warmup 2 --no-bs1 --no-llama --no-cpu-baseline --no-calibration --no-graph-check > /tmp/pb$bs.log 2>&1
   python $GRAFT_REPO_ROOT/tools/step_breakdown.py /tmp/pb$bs/t_results.db 8 > $out/step_breakdown_bs$bs.txt
   python $GRAFT_REPO_ROOT/tools/rocpd_stats.py /tmp/pb$bs/t_results.db > $out/kerneltrace_bs$bs.txt
 done
@@ -38,6 +39,6 @@ PARITY=0 python $GRAFT_REPO_ROOT/tools/mla_prefill_kernel_bench.py 512 1024 2048
 python $GRAFT_REPO_ROOT/tools/gqa_prefill_kernel_bench.py 512 2048 8192 > $out/gqa_prefill_kernel.txt 2>&1
 python $GRAFT_REPO_ROOT/tools/hw_cases_bench.py > $out/hw_cases_bench.txt 2>/dev/null
 for bs in 4 8 64; do
-  python $GRAFT_REPO_ROOT/bench.py --bs $bs --steps 32 --warmup 4 --no-bs1 --no-llama --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 >> $out/bs_sweep.jsonl
+  python "$repo/bench.py" --full --bs $bs --steps 32 --warmup 4 --no-bs1 --no-llama --no-cpu-baseline --no-roofline 2>/dev/null | tail -1 >> $out/bs_sweep.jsonl
 done
 ls -la $out
