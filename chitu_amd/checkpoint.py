@@ -326,13 +326,32 @@ def load_deepseek_v3(model: torch.nn.Module, state: Mapping[str, torch.Tensor], 
             mod._w_uk_key = None  # rebuilt in place on next use: buffers captured by hipGraphs stay valid
 
 
+def experts_to_mxfp4(state: Mapping[str, torch.Tensor], device) -> Dict[str, torch.Tensor]:
+    """Module-named state with fp8 block-scaled stacked experts (`*.ffn.w1w3_weight` / `w2_weight` [E, rows, K] e4m3 +
+    `*_scale` [E, ceil(rows/128), K/128]) -> the same names holding OCP MXFP4 (packed uint8 [E, rows, K/2] + E8M0 uint8
+    [E, rows, K/32]) of the dequantised values; converted on `device` by the HIP quantiser, one stacked tensor at a time."""
+    from .quantize.mxfp4 import quant_mxfp4_from_fp8_block
+
+    out = dict(state)
+    for k, t in state.items():
+        m = re.match(r"^(.*\.ffn\.(?:w1w3|w2))_weight$", k)
+        if m and t.dim() == 3 and t.dtype == torch.float8_e4m3fn:
+            packed, scales = quant_mxfp4_from_fp8_block(t.to(device), state[m.group(1) + "_scale"].to(device))
+            out[k], out[m.group(1) + "_scale"] = packed, scales
+    return out
+
+
 def load_checkpoint_deepseek_v3(model, path: str, rank: int = 0, world: int = 1, skip_preprocess: bool = False) -> None:
-    """HF directory (or a directory written by `save_preprocessed`) -> `model`, one call."""
+    """HF directory (or a directory written by `save_preprocessed`) -> `model`, one call.  A model built with
+    expert_dtype="mxfp4" gets its experts converted from the checkpoint's fp8 block format on the model's device
+    (`experts_to_mxfp4`); a preprocessed directory of such a model already holds the uint8 tensors."""
     args = model.args
     state = read_safetensors_dir(path, skip_preprocess=skip_preprocess, rank=rank, n_layers=args.n_layers)
     if not skip_preprocess:
         state = to_module_names(preprocess_deepseek_v3(state, args.n_routed_experts, rank, world,
                                                        moe_world_size=args.moe_world_size), args.q_lora_rank)
+        if getattr(args, "expert_dtype", "fp8") == "mxfp4":
+            state = experts_to_mxfp4(state, next(model.parameters()).device)
     load_deepseek_v3(model, state)
 
 

@@ -69,6 +69,9 @@ class DeepSeekV3Args:
     # process's TP rank (an explicit value runs one rank's shard on a lone GPU, like shard_degree).
     moe_world_size: int = 1
     moe_rank: Optional[int] = None
+    # Storage of the routed (and, without expert parallelism, the stacked shared) experts: "fp8" = e4m3 + [128,128] block
+    # scales (the reference's), "mxfp4" = OCP MXFP4, packed e2m1 + one E8M0 byte per 32 k (W4A8: fused_experts(use_mxfp4_w4a8)).
+    expert_dtype: str = "fp8"
 
     def tp_degree(self):
         return self.shard_degree if self.shard_degree is not None else tp.get_tp_size()
@@ -440,6 +443,14 @@ class MoEDeepSeekV3(torch.nn.Module):
         else:
             self.inter = args.moe_inter_dim // tp_size
             E = self.n_routed + self.n_shared
+        assert args.expert_dtype in ("fp8", "mxfp4"), f"unknown expert_dtype {args.expert_dtype!r}"
+        self.mxfp4 = args.expert_dtype == "mxfp4"
+        if self.mxfp4:  # same names, uint8: two e2m1 per byte, one E8M0 scale byte per 32 k of a row
+            assert args.dim % BLOCK == 0 and self.inter % BLOCK == 0, "MXFP4 experts need whole 128-blocks"
+            u8 = lambda *shape: torch.nn.Parameter(torch.empty(*shape, dtype=torch.uint8, device=device), requires_grad=False)
+            self.w1w3_weight, self.w1w3_scale = u8(E, 2 * self.inter, args.dim // 2), u8(E, 2 * self.inter, args.dim // 32)
+            self.w2_weight, self.w2_scale = u8(E, args.dim, self.inter // 2), u8(E, args.dim, self.inter // 32)
+            return
         self.w1w3_weight = torch.nn.Parameter(torch.empty(E, 2 * self.inter, args.dim, dtype=FP8, device=device), requires_grad=False)
         self.w1w3_scale = torch.nn.Parameter(torch.empty(E, (2 * self.inter + BLOCK - 1) // BLOCK, args.dim // BLOCK, dtype=torch.float32, device=device), requires_grad=False)
         self.w2_weight = torch.nn.Parameter(torch.empty(E, args.dim, self.inter, dtype=FP8, device=device), requires_grad=False)
@@ -466,9 +477,10 @@ class MoEDeepSeekV3(torch.nn.Module):
         weights, indices = routed[0], routed[1]
         aligned = routed[2] if len(routed) > 2 else None
         return fused_moe.fused_experts(
-            x, self.w1w3_weight, self.w2_weight, topk_weights=weights, topk_ids=indices, use_fp8_w8a8=True,
+            x, self.w1w3_weight, self.w2_weight, topk_weights=weights, topk_ids=indices, use_fp8_w8a8=not self.mxfp4,
             inplace=True, global_num_experts=nr + ns, w1_scale=self.w1w3_scale, w2_scale=self.w2_scale,
             block_shape=[BLOCK, BLOCK], a1_quant=x_quant, reduce_topk=not defer_sum, aligned=aligned,
+            use_mxfp4_w4a8=self.mxfp4,
         )
 
     def forward_expert_parallel(self, x, x_quant):
@@ -482,10 +494,10 @@ class MoEDeepSeekV3(torch.nn.Module):
         routed = self.gate(x, align=align)
         weights, indices = routed[0], routed[1]
         y = fused_moe.fused_experts(
-            x, self.w1w3_weight, self.w2_weight, topk_weights=weights, topk_ids=indices, use_fp8_w8a8=True,
+            x, self.w1w3_weight, self.w2_weight, topk_weights=weights, topk_ids=indices, use_fp8_w8a8=not self.mxfp4,
             inplace=True, global_num_experts=self.n_routed, expert_map=self.expert_map, w1_scale=self.w1w3_scale,
             w2_scale=self.w2_scale, block_shape=[BLOCK, BLOCK], a1_quant=x_quant,
-            aligned=routed[2] if len(routed) > 2 else None,
+            aligned=routed[2] if len(routed) > 2 else None, use_mxfp4_w4a8=self.mxfp4,
         )
         if self.shared is not None:
             y += self.shared(x_quant)
@@ -740,6 +752,13 @@ def init_synthetic_(model: torch.nn.Module, seed: int = 0, router_std: float = N
     for name, p in model.named_parameters():
         if p.dtype == FP8:
             _fill_fp8(p.data, gen)
+        elif p.dtype == torch.uint8:
+            # MXFP4 experts (the only uint8 parameters): every nibble is a valid e2m1 code, so the packed bytes are uniform;
+            # scale bytes 118..120 (2^-9 .. 2^-7) give weights of the fp8 experts' magnitude (mean |w| about 0.01)
+            if name.endswith("_scale"):
+                p.data.copy_(torch.randint(118, 121, p.shape, device=dev, generator=gen, dtype=torch.uint8))
+            else:
+                p.data.copy_(torch.randint(0, 256, p.shape, device=dev, generator=gen, dtype=torch.uint8))
         elif p.dtype == torch.float32:
             p.data.copy_(torch.rand(p.shape, device=dev, generator=gen) * 0.02 + 0.01)
         elif name.endswith("norm.weight"):

@@ -186,6 +186,7 @@ def fused_experts(
     reduce_topk: bool = True,
     use_int8_w8a8: bool = False,
     aligned=None,
+    use_mxfp4_w4a8: bool = False,
 ) -> torch.Tensor:
     """Same signature as chitu/fused_moe.py:1060-1127 (+ optional a1_quant / reduce_topk, see fused_experts_impl).  (The reference's inplace=False branch
     calls an unregistered torch.ops.vllm op; here both branches work.)"""
@@ -193,7 +194,7 @@ def fused_experts(
         hidden_states, w1, w2, topk_weights, topk_ids, inplace, activation, use_fp8_w8a8,
         use_int8_w8a16, use_int4_w4a16, global_num_experts, expert_map, w1_scale, w2_scale, w1_zp,
         w2_zp, a1_scale, a2_scale, block_shape, soft_fp8=soft_fp8, a1_quant=a1_quant, reduce_topk=reduce_topk,
-        use_int8_w8a8=use_int8_w8a8, aligned=aligned,
+        use_int8_w8a8=use_int8_w8a8, aligned=aligned, use_mxfp4_w4a8=use_mxfp4_w4a8,
     )
 
 
@@ -222,6 +223,7 @@ def fused_experts_impl(
     reduce_topk: bool = True,
     use_int8_w8a8: bool = False,
     aligned=None,
+    use_mxfp4_w4a8: bool = False,
 ):
     """out[t] = sum_j w[t,j] * W2[e_tj] . (silu(W1[e_tj] x_t)[:I] * (W1[e_tj] x_t)[I:])
 
@@ -238,7 +240,14 @@ def fused_experts_impl(
     aligned=(sorted_token_ids, expert_ids, num_tokens_post_pad): moe_align_block_size(topk_ids, 16,
     global_num_experts, expert_map) already computed by the producer of topk_ids
     (ops.gate_deepseek_v3(align=...): routing and sort in one launch) -- skips the align launch.
+    use_mxfp4_w4a8=True: OCP MXFP4 expert weights (packed e2m1 + E8M0 block scales) with the fp8 path's activations and
+    rounding points -- `_fused_experts_mxfp4`.
     """
+    if use_mxfp4_w4a8:  # before the hidden-size assert: here w1.shape[2] is K/2
+        if activation != "silu":
+            raise ValueError(f"Unsupported FusedMoe activation: {activation}")
+        return _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, expert_map,
+                                    w1_scale, w2_scale, a1_quant, reduce_topk, aligned)
     assert hidden_states.shape[1] == w1.shape[2], "Hidden size mismatch"
     assert topk_weights.shape == topk_ids.shape, "topk shape mismatch"
     assert hidden_states.is_contiguous(), "Hidden_states must be contiguous"
@@ -413,6 +422,108 @@ def fused_experts_impl(
             ),
             "moe gemm2",
         )
+    if not reduce_topk:
+        c3_off = off["c3"] - base
+        return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
+    check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
+    return out
+
+
+def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, expert_map,
+                         w1_scale, w2_scale, a1_quant, reduce_topk, aligned):
+    """W4A8: MXFP4 experts (OCP MX v1.0; chitu_amd.quantize.mxfp4), e4m3 activations.  w1 uint8 [E, 2I, K/2] (two e2m1 per
+    byte, even k in the low nibble) with w1_scale uint8 [E, 2I, K/32] (E8M0, one byte per 32 k); w2 uint8 [E, Nout, I/2] with
+    w2_scale uint8 [E, Nout, I/32]; K % 128 == 0 and I % 128 == 0.  The arithmetic is the fp8 path's with the weight operand
+    exchanged: activations quantised to e4m3 per 128-group, the 128-wide block dot is one scaled MFMA that applies the
+    weights' E8M0 bytes in hardware, its fp32 result times the activation's group scale accumulates in fp32, GEMM1 -> bf16,
+    SiLU-and-mul on bf16, h re-quantised per 128-group, routed weight on GEMM2's accumulator, top-k sum in fp32.
+    align(16) -> [quant ->] GEMM1 + silu*mul -> requant + GEMM2 -> sum (experts wider than 512: GEMM1, silu_mul_quant,
+    GEMM2), csrc/moe_mxfp4.hip, in the persistent workspace (graph-capture safe).  inplace / global_num_experts /
+    expert_map / a1_quant / reduce_topk / aligned mean what they mean on the fp8 path.
+    The 16-slot weight-streaming form is used at EVERY token count: there is no compute-shaped (prefill) MXFP4 GEMM, so a
+    prefill-sized call is correct and slow (each 16-slot tile streams its expert's weights again)."""
+    assert topk_weights.shape == topk_ids.shape, "topk shape mismatch"
+    assert hidden_states.dim() == 2 and hidden_states.is_contiguous(), "Hidden_states must be contiguous"
+    assert hidden_states.dtype == torch.bfloat16, "bf16 activations"
+    assert w1_scale is not None and w2_scale is not None, "MXFP4 experts need their E8M0 scales"
+    for t in (w1, w2, w1_scale, w2_scale):
+        assert t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3, "MXFP4 weights and scales are contiguous uint8 [E, rows, .]"
+    num_tokens, K = hidden_states.shape
+    E, N, _ = w1.shape
+    I = N // 2
+    Nout = w2.shape[1]
+    assert K % 128 == 0 and I % 128 == 0 and N == 2 * I, "K and the expert width must be multiples of 128"
+    assert tuple(w1.shape) == (E, N, K // 2) and tuple(w1_scale.shape) == (E, N, K // 32), "w1 [E, 2I, K/2], w1_scale [E, 2I, K/32]"
+    assert tuple(w2.shape) == (E, Nout, I // 2) and tuple(w2_scale.shape) == (E, Nout, I // 32), "w2 [E, Nout, I/2], w2_scale [E, Nout, I/32]"
+    require_cuda(hidden_states, w1, w2, topk_weights, topk_ids, w1_scale, w2_scale)
+    if global_num_experts == -1:
+        global_num_experts = E
+    topk = topk_ids.shape[1]
+    dev = hidden_states.device
+    out = hidden_states if inplace else torch.empty_like(hidden_states)
+    if num_tokens == 0:
+        return out
+    assert Nout == K or not reduce_topk, "the summed output has the hidden size"
+    numel = num_tokens * topk
+    topk_ids = topk_ids.contiguous()
+    topk_weights = topk_weights.contiguous()
+    cap = numel + global_num_experts * (_MOE_BLOCK_M - 1)
+    nblk = ceil_div(cap, _MOE_BLOCK_M)
+    KB = K // 128
+    rnd = lambda n: (n + 255) // 256 * 256
+    sizes = [("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
+             ("a1q", num_tokens * K), ("a1s", num_tokens * KB * 4), ("c1", numel * N * 2),
+             ("a2q", numel * I), ("a2s", numel * (I // 128) * 4), ("c3", numel * Nout * 2)]
+    ws = workspace.get(sum(rnd(n) for _, n in sizes), dev, "moe")
+    base, off, cur = ws.data_ptr(), {}, 0
+    for name, n in sizes:
+        off[name] = base + cur
+        cur += rnd(n)
+    import ctypes as _ct
+
+    P = lambda name: _ct.c_void_p(off[name])
+    lib, st = _lib.lib(), stream_ptr()
+    max_mblocks = min(nblk, numel)
+    if aligned is None:
+        emap = _expert_map_i32(expert_map, global_num_experts, dev)
+        check(lib.chitu_hip_moe_align_block_size_mapped(ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel),
+                                                        i32(global_num_experts), i32(_MOE_BLOCK_M), P("sorted"), i64(cap),
+                                                        P("experts"), i64(nblk), P("npost"), P("cumsum"), i32(1), ptr(emap), st),
+              "moe_align_block_size")
+        sorted_p, experts_p, npost_p = P("sorted"), P("experts"), P("npost")
+    else:
+        a_sorted, a_experts, a_npost = aligned
+        require_cuda(a_sorted, a_experts, a_npost)
+        assert a_sorted.dtype == torch.int32 and a_experts.dtype == torch.int32 and a_npost.dtype == torch.int32
+        assert a_sorted.numel() == cap and a_experts.numel() == nblk, "aligned buffers must come from block 16 over global_num_experts"
+        sorted_p, experts_p, npost_p = ptr(a_sorted), ptr(a_experts), ptr(a_npost)
+    if a1_quant is None:
+        check(lib.chitu_hip_act_quant_fp8(ptr(hidden_states), float_dtype_code(hidden_states.dtype), i64(num_tokens), i64(K),
+                                          i32(128), i32(1), f32(1e-10), P("a1q"), P("a1s"), st), "moe quant1")
+        a1q_p, a1s_p = P("a1q"), P("a1s")
+    else:
+        aq, as_ = a1_quant
+        require_cuda(aq, as_)
+        assert aq.is_contiguous() and as_.is_contiguous() and aq.element_size() == 1 and aq.numel() == num_tokens * K
+        assert as_.dtype == torch.float32 and as_.numel() == num_tokens * KB
+        a1q_p, a1s_p = ptr(aq), ptr(as_)
+    wdt = float_dtype_code(topk_weights.dtype)
+    if I <= 512:
+        check(lib.chitu_hip_moe_gemm1_silu_mxfp4(a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
+                                                 i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), st),
+              "moe mxfp4 gemm1 (silu fused)")
+        check(lib.chitu_hip_moe_gemm2_quant_mxfp4(P("c1"), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
+                                                  ptr(topk_weights), i32(wdt), i32(1), P("c3"), i64(numel), i64(Nout), i64(I),
+                                                  i64(max_mblocks), f32(1e-10), st), "moe mxfp4 gemm2 (quant fused)")
+    else:  # wide experts: the three-launch form, as on the fp8 path
+        check(lib.chitu_hip_moe_gemm_mxfp4(a1q_p, a1s_p, i32(topk), ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p,
+                                           ptr(None), i32(0), i32(0), P("c1"), i64(numel), i64(N), i64(K), i64(max_mblocks), st),
+              "moe mxfp4 gemm1")
+        check(lib.chitu_hip_moe_silu_mul_quant_fp8(P("c1"), i64(numel), i64(I), i32(1), f32(1e-10), P("a2q"), P("a2s"), st),
+              "moe silu_mul_quant")
+        check(lib.chitu_hip_moe_gemm_mxfp4(P("a2q"), P("a2s"), i32(1), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
+                                           ptr(topk_weights), i32(wdt), i32(1), P("c3"), i64(numel), i64(Nout), i64(I),
+                                           i64(max_mblocks), st), "moe mxfp4 gemm2")
     if not reduce_topk:
         c3_off = off["c3"] - base
         return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)

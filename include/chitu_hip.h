@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 3  /* 3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 4  /* 4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -207,6 +207,46 @@ int chitu_hip_moe_gemm2_quant_fp8(const void* h_bf16, const void* w2_fp8, const 
                                   float eps, void* stream);
 int chitu_hip_moe_sum(const void* c3_bf16, void* out_bf16, int64_t tokens, int32_t topk, int64_t N,
                       void* stream);
+
+/* ---- fused MoE with MXFP4 expert weights, W4A8 (csrc/moe_mxfp4.hip) -----------------------------
+ * OCP MX v1.0 weights: packed e2m1, two per byte (low nibble = even k), uint8 [E, rows, K/2], with one E8M0 scale byte per 32
+ * consecutive k of a row, uint8 [E, rows, K/32] (value 2^(byte - 127); 0xFF = NaN).  Activations are e4m3 with per-128-group
+ * fp32 scales exactly as in the fp8 entries above; the 128-wide block dot is one v_mfma_scale_f32_16x16x128_f8f6f4 with the
+ * weights' own scale bytes as the hardware scale operand, its fp32 result is multiplied by the activation's group scale and
+ * accumulated in fp32.  Everything else (padding slots, expert -1 = zeros, the num_tokens_post_pad early exit, rounding
+ * points) is the fp8 entries'.  sorted_token_ids / expert_ids / num_tokens_post_pad: moe_align with block_size 16.
+ * K % 128 == 0 and inter_size % 128 == 0, one expert's matrix below 2^31 bytes (CHITU_ERR_UNSUPPORTED otherwise).
+ *   chitu_hip_moe_gemm1_silu_mxfp4  replaces chitu_hip_moe_gemm1_silu_fp8 for MXFP4 W1 [E, 2I, K/2].
+ *   chitu_hip_moe_gemm2_quant_mxfp4 replaces chitu_hip_moe_gemm2_quant_fp8 for MXFP4 W2 [E, N, I/2]; inter_size <= 512.
+ *   chitu_hip_moe_gemm_mxfp4        replaces chitu_hip_moe_gemm1_fp8 (a_div = topk, mul_routed_weight = 0) and
+ *     chitu_hip_moe_gemm2_fp8 (a_div = 1) of the three-launch form: out[slot, :] = bf16((a[slot / a_div] . W[e]^T) * weight).
+ *   chitu_hip_quant_mxfp4           new: no reference counterpart.  src_kind 0 / 1 / 2: bf16 / f16 / f32 [rows, cols]; 3: e4m3
+ *     [rows, cols] times the fp32 scale of its [128, 128] block, block_scale [rows / rows_per_matrix,
+ *     ceil(rows_per_matrix / 128), cols / 128].  Per 32-block: byte = clamp(exponent field of max|v| - 2, 0, 254), i.e. the OCP
+ *     shared exponent floor(log2 max|v|) - 2 (an all-zero block gets byte 0); elements = round-to-nearest-even of
+ *     v * 2^(127 - byte) onto {0, .5, 1, 1.5, 2, 3, 4, 6}, saturated at 6.  cols % 32 == 0 (kind 3: % 128).
+ *   chitu_hip_dequant_mxfp4         new: no reference counterpart.  out bf16 [rows, cols] = e2m1 x 2^(byte - 127), exact for
+ *     bytes 2..252 (outside that range the product may leave bf16's normal range: unspecified); 0xFF -> NaN. */
+int chitu_hip_moe_gemm1_silu_mxfp4(const void* a_fp8, const float* a_scale, const void* w1_fp4,
+                                   const void* w1_scale_e8m0, const int32_t* sorted_token_ids,
+                                   const int32_t* expert_ids, const int32_t* num_tokens_post_pad, void* h_bf16,
+                                   int64_t numel, int32_t topk, int64_t inter_size, int64_t K,
+                                   int64_t max_mblocks, void* stream);
+int chitu_hip_moe_gemm2_quant_mxfp4(const void* h_bf16, const void* w2_fp4, const void* w2_scale_e8m0,
+                                    const int32_t* sorted_token_ids, const int32_t* expert_ids,
+                                    const int32_t* num_tokens_post_pad, const void* topk_weights,
+                                    int32_t weights_dtype, int32_t mul_routed_weight, void* out_bf16,
+                                    int64_t numel, int64_t N, int64_t inter_size, int64_t max_mblocks, float eps,
+                                    void* stream);
+int chitu_hip_moe_gemm_mxfp4(const void* a_fp8, const float* a_scale, int32_t a_div, const void* w_fp4,
+                             const void* w_scale_e8m0, const int32_t* sorted_token_ids, const int32_t* expert_ids,
+                             const int32_t* num_tokens_post_pad, const void* topk_weights, int32_t weights_dtype,
+                             int32_t mul_routed_weight, void* out_bf16, int64_t numel, int64_t N, int64_t K,
+                             int64_t max_mblocks, void* stream);
+int chitu_hip_quant_mxfp4(const void* src, int32_t src_kind, const float* block_scale, int64_t rows, int64_t cols,
+                          int64_t rows_per_matrix, void* packed_fp4, void* scale_e8m0, void* stream);
+int chitu_hip_dequant_mxfp4(const void* packed_fp4, const void* scale_e8m0, int64_t rows, int64_t cols,
+                            void* out_bf16, void* stream);
 
 /* ---- fused MoE with bf16 ACTIVATIONS: bf16 experts and soft-fp8 experts (csrc/moe_bf16.hip) --------
  * The two modes of fused_moe_kernel (chitu/fused_moe.py:62-307) that do not quantise the activations:
