@@ -150,7 +150,23 @@ _MOE_TILED_MIN_PER_EXPERT = 24
 # Slots per tile = moe_align block of the tiled path: 128 (round 6: one pass over an expert's weights for up to 128 slots, padding
 # sub-tiles skipped) or 64 (rounds 2-5, the reference's BLOCK_SIZE_M); same outputs, A/B in profiles/r06_ab_moe_tiled128.txt
 _MOE_TILED_BLOCK_M = int(os.environ.get("CHITU_MOE_TILED_BLOCK_M", "128"))
+# MXFP4 experts switch over later: their streaming kernels move half the bytes per 16-slot tile, so re-streaming an expert's
+# weights costs less.  R1 rank shard, forced forms (tools/moe_mxfp4_ab.py --prefill, profiles/mxfp4_moe_prefill_ab.json):
+# us per layer, streaming / tiled: 128 tokens 195 / 263, 256: 228 / 277, 384: 273 / 286, 512: 355 / 299, 1024: 592 / 369, 2048: 1068 / 481 --
+# 512 is the smallest measured count at which the tiled form wins.  (The per-expert floor above still applies.)
+_MOE_MXFP4_TILED_MIN_TOKENS = int(os.environ.get("CHITU_MOE_MXFP4_TILED_MIN_TOKENS", "512"))
 
+
+
+def _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, min_tokens=None):
+    """Whether a fused_experts call takes the compute-shaped (tiled, prefill) expert GEMMs instead of the 16-slot streaming
+    ones: one rule for the fp8 experts (csrc/moe_tiled.hip) and the MXFP4 experts (csrc/moe_mxfp4_tiled.hip).  A
+    caller-supplied `aligned` comes from moe_align with block 16 and keeps the streaming form.  min_tokens: the token count
+    from which the caller's format switches over (default: the fp8 path's _MOE_TILED_MIN_TOKENS, which at 0 switches the
+    tiled form off for every format)."""
+    floor = _MOE_TILED_MIN_TOKENS if min_tokens is None else min_tokens
+    return (_MOE_TILED_MIN_TOKENS > 0 and floor > 0 and num_tokens >= floor and aligned is None and I % 128 == 0
+            and Nout % 8 == 0 and numel >= _MOE_TILED_MIN_PER_EXPERT * global_num_experts)
 
 class SiluAndMul(torch.nn.Module):
     """x -> silu(x[..., :d]) * x[..., d:]  (chitu/fused_moe.py:24-39).  Kept for API parity; the
@@ -299,8 +315,7 @@ def fused_experts_impl(
     def rnd(n):
         return (n + 255) // 256 * 256
 
-    tiled = (_MOE_TILED_MIN_TOKENS > 0 and num_tokens >= _MOE_TILED_MIN_TOKENS and aligned is None and I % 128 == 0
-             and Nout % 8 == 0 and numel >= _MOE_TILED_MIN_PER_EXPERT * global_num_experts)
+    tiled = _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned)
     block_m = _MOE_TILED_BLOCK_M if tiled else _MOE_BLOCK_M
     cap = numel + global_num_experts * (block_m - 1)
     nblk = ceil_div(cap, block_m)
@@ -440,8 +455,10 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
     align(16) -> [quant ->] GEMM1 + silu*mul -> requant + GEMM2 -> sum (experts wider than 512: GEMM1, silu_mul_quant,
     GEMM2), csrc/moe_mxfp4.hip, in the persistent workspace (graph-capture safe).  inplace / global_num_experts /
     expert_map / a1_quant / reduce_topk / aligned mean what they mean on the fp8 path.
-    The 16-slot weight-streaming form is used at EVERY token count: there is no compute-shaped (prefill) MXFP4 GEMM, so a
-    prefill-sized call is correct and slow (each 16-slot tile streams its expert's weights again)."""
+    Prefill-sized calls (`_takes_tiled`, the fp8 path's rule from _MOE_MXFP4_TILED_MIN_TOKENS tokens on) take the compute-shaped form instead: align(_MOE_TILED_BLOCK_M)
+    -> [quant ->] GEMM1 + silu*mul tiled -> quant of h -> GEMM2 tiled -> sum (csrc/moe_mxfp4_tiled.hip), for every expert width.
+    Both forms are the same fma chain over the same hardware block dots: with the streaming kernels' K split off
+    (debug_option moe_gemm1_wk = 1) their outputs are the same bits."""
     assert topk_weights.shape == topk_ids.shape, "topk shape mismatch"
     assert hidden_states.dim() == 2 and hidden_states.is_contiguous(), "Hidden_states must be contiguous"
     assert hidden_states.dtype == torch.bfloat16, "bf16 activations"
@@ -467,8 +484,10 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
     numel = num_tokens * topk
     topk_ids = topk_ids.contiguous()
     topk_weights = topk_weights.contiguous()
-    cap = numel + global_num_experts * (_MOE_BLOCK_M - 1)
-    nblk = ceil_div(cap, _MOE_BLOCK_M)
+    tiled = _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, min_tokens=_MOE_MXFP4_TILED_MIN_TOKENS)
+    block_m = _MOE_TILED_BLOCK_M if tiled else _MOE_BLOCK_M
+    cap = numel + global_num_experts * (block_m - 1)
+    nblk = ceil_div(cap, block_m)
     KB = K // 128
     rnd = lambda n: (n + 255) // 256 * 256
     sizes = [("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
@@ -487,7 +506,7 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
     if aligned is None:
         emap = _expert_map_i32(expert_map, global_num_experts, dev)
         check(lib.chitu_hip_moe_align_block_size_mapped(ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel),
-                                                        i32(global_num_experts), i32(_MOE_BLOCK_M), P("sorted"), i64(cap),
+                                                        i32(global_num_experts), i32(block_m), P("sorted"), i64(cap),
                                                         P("experts"), i64(nblk), P("npost"), P("cumsum"), i32(1), ptr(emap), st),
               "moe_align_block_size")
         sorted_p, experts_p, npost_p = P("sorted"), P("experts"), P("npost")
@@ -508,7 +527,18 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
         assert as_.dtype == torch.float32 and as_.numel() == num_tokens * KB
         a1q_p, a1s_p = ptr(aq), ptr(as_)
     wdt = float_dtype_code(topk_weights.dtype)
-    if I <= 512:
+    if tiled:
+        # prefill: GEMM1 + SiLU-and-mul tiled, per-token-group quant of h, GEMM2 tiled (csrc/moe_mxfp4_tiled.hip)
+        assert nblk <= 65535
+        check(lib.chitu_hip_moe_gemm1_silu_mxfp4_tiled(a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
+                                                       i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), i32(block_m), st),
+              "moe mxfp4 gemm1 (tiled, silu fused)")
+        check(lib.chitu_hip_act_quant_fp8(P("c1"), float_dtype_code(torch.bfloat16), i64(numel), i64(I), i32(128), i32(1),
+                                          f32(1e-10), P("a2q"), P("a2s"), st), "moe quant2")
+        check(lib.chitu_hip_moe_gemm2_mxfp4_tiled(P("a2q"), P("a2s"), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
+                                                  ptr(topk_weights), i32(wdt), i32(1), P("c3"), i64(numel), i64(Nout), i64(I),
+                                                  i64(max_mblocks), i32(block_m), st), "moe mxfp4 gemm2 (tiled)")
+    elif I <= 512:
         check(lib.chitu_hip_moe_gemm1_silu_mxfp4(a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
                                                  i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), st),
               "moe mxfp4 gemm1 (silu fused)")

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 4  /* 4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 5  /* 5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -247,6 +247,32 @@ int chitu_hip_quant_mxfp4(const void* src, int32_t src_kind, const float* block_
                           int64_t rows_per_matrix, void* packed_fp4, void* scale_e8m0, void* stream);
 int chitu_hip_dequant_mxfp4(const void* packed_fp4, const void* scale_e8m0, int64_t rows, int64_t cols,
                             void* out_bf16, void* stream);
+
+/* ---- fused MoE with MXFP4 expert weights, PREFILL-sized batches (csrc/moe_mxfp4_tiled.hip) ---------
+ * The two grouped GEMMs above tiled for compute: block_m (64 or 128) sorted slots x 128 weight rows per workgroup, both
+ * operand tiles and the E8M0 bytes staged in LDS by LDS-DMA.  sorted_token_ids / expert_ids / num_tokens_post_pad: moe_align
+ * with block_size = block_m; a block whose first slot is padding is skipped, expert -1 writes zeros, as in the fp8 tiled
+ * entries, whose argument lists these share (weight and scale pointers exchanged for the MXFP4 pair).  Arithmetic: the block
+ * dot and the ascending fmaf chain of the streaming entries, one chain per output (no K split): the same bits as
+ * chitu_hip_moe_gemm1_silu_mxfp4 / chitu_hip_moe_gemm_mxfp4 launched without their K split.
+ * K % 128 == 0, inter_size % 128 == 0, N % 8 == 0, block_m in {64, 128}, one expert's matrix and the activation matrix below
+ * 2^31 bytes (CHITU_ERR_UNSUPPORTED otherwise); numel == 0 or max_mblocks == 0 is CHITU_OK with nothing launched.
+ *   chitu_hip_moe_gemm1_silu_mxfp4_tiled  new: no reference counterpart; tiled form of chitu_hip_moe_gemm1_silu_mxfp4
+ *     (h = bf16(bf16(silu(bf16(g))) * bf16(u)), bf16 [numel, I]), the MXFP4 counterpart of chitu_hip_moe_gemm1_silu_fp8_tiled.
+ *   chitu_hip_moe_gemm2_mxfp4_tiled       new: no reference counterpart; tiled form of chitu_hip_moe_gemm_mxfp4 with
+ *     a_div = 1 (out[slot, :] = bf16((h_fp8[slot] . W2[e]^T) * routed_weight[slot]); h quantised by the caller with
+ *     chitu_hip_act_quant_fp8 mode 1), the MXFP4 counterpart of chitu_hip_moe_gemm2_fp8_tiled. */
+int chitu_hip_moe_gemm1_silu_mxfp4_tiled(const void* a_fp8, const float* a_scale, const void* w1_fp4,
+                                         const void* w1_scale_e8m0, const int32_t* sorted_token_ids,
+                                         const int32_t* expert_ids, const int32_t* num_tokens_post_pad,
+                                         void* h_bf16, int64_t numel, int32_t topk, int64_t inter_size, int64_t K,
+                                         int64_t max_mblocks, int32_t block_m, void* stream);
+int chitu_hip_moe_gemm2_mxfp4_tiled(const void* h_fp8, const float* h_scale, const void* w2_fp4,
+                                    const void* w2_scale_e8m0, const int32_t* sorted_token_ids,
+                                    const int32_t* expert_ids, const int32_t* num_tokens_post_pad,
+                                    const void* topk_weights, int weights_dtype, int32_t mul_routed_weight,
+                                    void* out_bf16, int64_t numel, int64_t N, int64_t inter_size,
+                                    int64_t max_mblocks, int32_t block_m, void* stream);
 
 /* ---- fused MoE with bf16 ACTIVATIONS: bf16 experts and soft-fp8 experts (csrc/moe_bf16.hip) --------
  * The two modes of fused_moe_kernel (chitu/fused_moe.py:62-307) that do not quantise the activations:

@@ -14,7 +14,14 @@ Writes one JSON document (--out).  One GPU process; nothing else is started.
 
 --step: instead, time a whole DeepSeek-R1 TP=8 rank-shard decode step (61 layers, bs 16, ctx 1024, greedy, hipGraph; bench.py's
 workload) with fp8 and then with MXFP4 experts, each in a fresh child process under its own time limit, one after the other
-(this process never opens the GPU); a child that fails ends the run.  The result is merged into --out under "whole_step"."""
+(this process never opens the GPU); a child that fails ends the run.  The result is merged into --out under "whole_step".
+
+--prefill T [T ...]: instead, the routed-expert launch sequence of one PREFILL call of T prompt tokens (fused_experts: align, quant,
+GEMM1 + SiLU-and-mul, [quant of h,] GEMM2, top-k sum), same shapes (every token picks 8 random routed experts and the shared one), timed
+three ways in one process: fp8 experts tiled (csrc/moe_tiled.hip), MXFP4 experts streaming (csrc/moe_mxfp4.hip, the 16-slot decode
+kernels: CHITU_MOE_TILED_MIN_TOKENS=0) and MXFP4 experts tiled (csrc/moe_mxfp4_tiled.hip).  The form is FORCED per arm (the
+per-expert slot floor of fused_moe._takes_tiled is lifted), and what the dispatch rule itself would pick at T is recorded beside
+the times.  Each arm is one hipGraph of `--layers` calls on different weight sets (cold weights); the graphs are replayed alternately."""
 import argparse
 import json
 import os
@@ -33,6 +40,7 @@ ap.add_argument("--bs", type=int, nargs="+", default=[1, 16])
 ap.add_argument("--layers", type=int, default=6, help="weight sets rotated through (each launch of a replay uses another one)")
 ap.add_argument("--repeats", type=int, default=21)
 ap.add_argument("--warmup", type=int, default=3)
+ap.add_argument("--prefill", type=int, nargs="+", default=[], help="prompt token counts: time the prefill-sized expert sequence three ways")
 ap.add_argument("--out", type=str, default="")
 ap.add_argument("--opt", type=str, default="", help="launch-variant overrides for a sweep, e.g. moe_gemm1_wk=2,moe_gemm1_d=2 (both arms)")
 a = ap.parse_args()
@@ -64,6 +72,21 @@ import torch  # noqa: E402
 
 from chitu_amd import _lib, fused_moe  # noqa: E402
 from chitu_amd._lib import f32, i32, i64, ptr, stream_ptr  # noqa: E402
+
+def alternate_graphs(graphs, per_replay, warmup, repeats):
+    """graphs: {arm: graph}; replays them in turn; returns {arm: [us per (replay / per_replay)]}."""
+    out = {k: [] for k in graphs}
+    for it in range(warmup + repeats):
+        for k, g in graphs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                out[k].append(e0.elapsed_time(e1) * 1e3 / per_replay)
+    return out
+
 
 if a.child_step:
     import time
@@ -110,6 +133,82 @@ if a.child_step:
     experts = sum(p.numel() * p.element_size() for n, p in model.named_parameters() if ".ffn.w1w3_" in n or ".ffn.w2_" in n)
     print(json.dumps({"expert_dtype": a.child_step, "ms_per_step": round(dt / a.steps * 1e3, 4), "steps": a.steps, "bs": a.step_bs,
                       "ctx": a.step_ctx, "expert_bytes_GB": round(experts / 1e9, 2), "logits_finite": bool(torch.isfinite(logits).all())}))
+    sys.exit(0)
+
+if a.prefill:
+    torch.cuda.set_device(0)
+    dev = "cuda"
+    gen = torch.Generator(device=dev).manual_seed(0)
+    FP8 = torch.float8_e4m3fn
+    E, K, I, TOPK, L = 257, 7168, 256, 9, a.layers
+
+    def chunked(t, fill):
+        flat = t.view(-1)
+        for i in range(0, flat.numel(), 1 << 26):
+            n = min(1 << 26, flat.numel() - i)
+            flat[i:i + n].copy_(fill(n))
+        return t
+
+    rfp8 = lambda *sh: chunked(torch.empty(*sh, dtype=FP8, device=dev), lambda n: (torch.randn(n, device=dev, dtype=torch.bfloat16, generator=gen) * 0.5).to(FP8))
+    ru8 = lambda lo, hi, *sh: torch.randint(lo, hi, sh, device=dev, generator=gen, dtype=torch.uint8)
+    W8 = [(rfp8(E, 2 * I, K), torch.rand(E, 4, K // 128, device=dev, generator=gen) * 0.02 + 0.01,
+           rfp8(E, K, I), torch.rand(E, K // 128, 2, device=dev, generator=gen) * 0.02 + 0.01) for _ in range(L)]
+    W4 = [(ru8(0, 256, E, 2 * I, K // 2), ru8(118, 121, E, 2 * I, K // 32), ru8(0, 256, E, K, I // 2), ru8(118, 121, E, K, I // 32))
+          for _ in range(L)]
+    layer_bytes = {"fp8": sum(t.numel() * t.element_size() for t in W8[0]), "mxfp4": sum(t.numel() for t in W4[0])}
+    result = {"shapes": {"E": E, "K": K, "I": I, "topk": TOPK, "layers": L, "block_m": fused_moe._MOE_TILED_BLOCK_M},
+              "layer_weight_bytes": layer_bytes, "tokens": {}}
+    defaults = (fused_moe._MOE_TILED_MIN_PER_EXPERT, fused_moe._MOE_TILED_MIN_TOKENS, fused_moe._MOE_MXFP4_TILED_MIN_TOKENS)
+
+    def force(tiled):
+        fused_moe._MOE_TILED_MIN_PER_EXPERT = 0
+        fused_moe._MOE_TILED_MIN_TOKENS = fused_moe._MOE_MXFP4_TILED_MIN_TOKENS = 1 if tiled else 0
+
+    for T in a.prefill:
+        x = torch.randn(T, K, device=dev, dtype=torch.bfloat16, generator=gen) * 0.5
+        ids = torch.stack([torch.randperm(E - 1, device=dev, generator=gen)[:TOPK - 1] for _ in range(T)])
+        ids = torch.cat([ids, torch.full((T, 1), E - 1, device=dev)], 1).contiguous()
+        wts = torch.rand(T, TOPK, device=dev, generator=gen).to(torch.bfloat16)
+
+        def call(arm, l):
+            if arm == "fp8_tiled":
+                w1, s1, w2, s2 = W8[l]
+                return lambda: fused_moe.fused_experts(x, w1, w2, wts, ids, use_fp8_w8a8=True, w1_scale=s1, w2_scale=s2, block_shape=[128, 128])
+            w1, s1, w2, s2 = W4[l]
+            return lambda: fused_moe.fused_experts(x, w1, w2, wts, ids, use_mxfp4_w4a8=True, w1_scale=s1, w2_scale=s2)
+
+        graphs, outs = {}, {}
+        for arm in ("fp8_tiled", "mxfp4_streaming", "mxfp4_tiled"):
+            force(arm != "mxfp4_streaming")
+            fns = [call(arm, l) for l in range(L)]
+            outs[arm] = fns[0]().clone()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                for f in fns:
+                    f()
+            g.replay()
+            torch.cuda.synchronize()
+            graphs[arm] = g
+        fused_moe._MOE_TILED_MIN_PER_EXPERT, fused_moe._MOE_TILED_MIN_TOKENS, fused_moe._MOE_MXFP4_TILED_MIN_TOKENS = defaults
+        us = alternate_graphs(graphs, L, a.warmup, a.repeats)
+        row = {arm: {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1), "repeats": len(v)}
+               for arm, v in us.items()}
+        same = (outs["mxfp4_tiled"].float() - outs["mxfp4_streaming"].float()).abs().max().item() / outs["mxfp4_streaming"].float().abs().max().item()
+        row["tiled_vs_streaming_peak_rel_diff"] = same
+        row["tiled_over_streaming"] = round(row["mxfp4_tiled"]["median_us"] / row["mxfp4_streaming"]["median_us"], 4)
+        row["mxfp4_tiled_over_fp8_tiled"] = round(row["mxfp4_tiled"]["median_us"] / row["fp8_tiled"]["median_us"], 4)
+        row["slots_per_expert"] = round(T * TOPK / E, 1)
+        row["dispatch_rule_takes_tiled"] = bool(fused_moe._takes_tiled(T, T * TOPK, E, I, K, None, min_tokens=fused_moe._MOE_MXFP4_TILED_MIN_TOKENS))
+        result["tokens"][str(T)] = row
+        print(f"{T:5d} tokens: fp8 tiled {row['fp8_tiled']['median_us']:.1f} us | mxfp4 streaming {row['mxfp4_streaming']['median_us']:.1f} us | "
+              f"mxfp4 tiled {row['mxfp4_tiled']['median_us']:.1f} us [{row['mxfp4_tiled']['min_us']:.1f} .. {row['mxfp4_tiled']['max_us']:.1f}] | "
+              f"tiled / streaming {row['tiled_over_streaming']:.3f} | mxfp4 tiled / fp8 tiled {row['mxfp4_tiled_over_fp8_tiled']:.3f} | "
+              f"rule picks {'tiled' if row['dispatch_rule_takes_tiled'] else 'streaming'} | outputs differ by {same:.1e} of the peak", flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(result, f, indent=1)
     sys.exit(0)
 
 for kv in filter(None, a.opt.split(",")):
@@ -168,18 +267,7 @@ def graph_of(fns):
 
 
 def alternate(graphs, per_replay):
-    """graphs: {arm: graph}; replays them in turn; returns {arm: [us per (replay / per_replay)]}."""
-    out = {k: [] for k in graphs}
-    for it in range(a.warmup + a.repeats):
-        for k, g in graphs.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            if it >= a.warmup:
-                out[k].append(e0.elapsed_time(e1) * 1e3 / per_replay)
-    return out
+    return alternate_graphs(graphs, per_replay, a.warmup, a.repeats)
 
 
 def stats(us, nbytes):
