@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 REL_TOL = 1e-2
 
 
-def make_case(M, E, topk, K, I, seed, w_dtype=torch.bfloat16, dup_free=True):
+def make_case(M, E, topk, K, I, seed, w_dtype=torch.bfloat16):
     g = torch.Generator().manual_seed(seed)
     x = (torch.randn(M, K, generator=g) * 0.5).to(torch.bfloat16)
     w1 = (torch.randn(E, 2 * I, K, generator=g) * 0.5).to(torch.float8_e4m3fn)

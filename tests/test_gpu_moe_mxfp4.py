@@ -18,20 +18,23 @@ REL_TOL = 1e-2
 
 # ---------------------------------------------------------------- lane map, exact integer data
 def _plain_gemm(aq, a_s, a_div, w, ws, ids, E, wts=None):
-    """chitu_hip_moe_gemm_mxfp4 on its own: out bf16 [numel, N]."""
+    """chitu_hip_moe_gemm_mxfp4 on its own: out bf16 [numel, N], between guard rows that must stay untouched."""
     from chitu_amd import _lib, fused_moe
     from chitu_amd._lib import check, i32, i64, ptr, stream_ptr
 
     numel, N = ids.numel(), w.shape[1]
     K = aq.shape[1]
     sorted_ids, expert_ids, npost = fused_moe.moe_align_block_size(ids.cuda(), 16, E)
-    out = torch.full((numel, N), float("nan"), dtype=torch.bfloat16, device="cuda")
+    guard = 4  # rows before and after the output, NaN like the output itself: a store to row numel (a padding slot's id) shows
+    full = torch.full((numel + 2 * guard, N), float("nan"), dtype=torch.bfloat16, device="cuda")
+    out = full[guard:guard + numel]
     keep = [aq.cuda(), a_s.cuda(), w.cuda(), ws.cuda(), None if wts is None else wts.cuda()]
     check(_lib.lib().chitu_hip_moe_gemm_mxfp4(ptr(keep[0]), ptr(keep[1]), i32(a_div), ptr(keep[2]), ptr(keep[3]), ptr(sorted_ids),
                                               ptr(expert_ids), ptr(npost), ptr(keep[4]), i32(2), i32(0 if wts is None else 1),
                                               ptr(out), i64(numel), i64(N), i64(K), i64(min(expert_ids.numel(), numel)),
                                               stream_ptr()), "moe_gemm_mxfp4")
     torch.cuda.synchronize()
+    assert torch.isnan(full[:guard]).all() and torch.isnan(full[guard + numel:]).all(), "moe_gemm_mxfp4 stored outside its output rows"
     return out.cpu()
 
 
