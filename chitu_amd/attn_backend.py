@@ -15,9 +15,14 @@ import torch
 
 from . import _lib, workspace
 from ._lib import check, f32, i32, i64, ptr, require_cuda, stream_ptr
-from .ops import append_to_paged_kv_cache
+from .ops import MLA_KV_FP8_ROW, append_mla_kv_fp8, append_to_paged_kv_cache
 
 __all__ = ["AttnBackend", "HipAttnBackend"]
+
+
+def is_fp8_mla_cache(kv_cache) -> bool:
+    """A layer of the fp8 latent KV cache (uint8 [pages, page, 656], cache_manager.mla_kv_layout("fp8"))?"""
+    return kv_cache.dtype == torch.uint8 and kv_cache.shape[-1] == MLA_KV_FP8_ROW
 
 
 # Upper bound of the KV splits of the GQA decode launch (graph-static: sized from the page table's width, not from the
@@ -134,15 +139,19 @@ class HipAttnBackend(AttnBackend):
 
         return_partials=True (fused consumer, ops.mla_merge_absorb_uv_quant_fp8): when the KV range is
         split, skip the merge pass and return (workspace, num_splits) instead of the output; with a
-        single split the output tensor is returned as usual."""
+        single split the output tensor is returned as usual.
+
+        kv_cache uint8 [pages, page, 656] (the fp8 latent cache): chitu_hip_mla_decode_kv_fp8, same arguments, same
+        workspace; the result is bit-identical to this call on ops.mla_kv_dequant_fp8(kv_cache)."""
         require_cuda(q_nope, q_pe, kv_cache, cache_seqlens_incl, block_table)
         assert kv_cache.ndim == 3 and kv_cache.is_contiguous()  # (num_blocks, block_size, dim)
-        assert kv_cache.dtype == torch.bfloat16 and q_nope.dtype == torch.bfloat16 and q_pe.dtype == torch.bfloat16
+        fp8_kv = is_fp8_mla_cache(kv_cache)
+        assert (kv_cache.dtype == torch.bfloat16 or fp8_kv) and q_nope.dtype == torch.bfloat16 and q_pe.dtype == torch.bfloat16
         assert block_table.dtype == torch.int32 and cache_seqlens_incl.dtype == torch.int32
         assert block_table.stride(1) == 1 and cache_seqlens_incl.is_contiguous()
         B, H, C = q_nope.shape
         R = q_pe.shape[-1]
-        assert kv_cache.shape[-1] == C + R
+        assert fp8_kv or kv_cache.shape[-1] == C + R
 
         def ok(t):
             return t.stride(-1) == 1 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0 and t.data_ptr() % 16 == 0
@@ -159,15 +168,16 @@ class HipAttnBackend(AttnBackend):
             out = torch.empty(B, H, C, dtype=torch.bfloat16, device=q_nope.device)
         need = B * H * num_splits * (C * 2 + 4) if num_splits > 1 else 0  # bf16 partial rows + fp32 LSE
         ws = workspace.get(max(need, 1), q_nope.device, "mla")
+        entry = _lib.lib().chitu_hip_mla_decode_kv_fp8 if fp8_kv else _lib.lib().chitu_hip_mla_decode
         check(
-            _lib.lib().chitu_hip_mla_decode(
+            entry(
                 ptr(q_nope), i64(q_nope.stride(0)), i64(q_nope.stride(1)), ptr(q_pe), i64(q_pe.stride(0)),
                 i64(q_pe.stride(1)), ptr(kv_cache), i64(kv_cache.shape[0]), i32(kv_cache.shape[1]),
                 ptr(block_table), i32(block_table.stride(0)), ptr(cache_seqlens_incl), f32(softmax_scale),
                 ptr(None if partials else out), i32(B), i32(H), i32(C), i32(R), i32(num_splits), ptr(ws),
                 i64(ws.numel()), stream_ptr(),
             ),
-            "mla_decode",
+            "mla_decode_kv_fp8" if fp8_kv else "mla_decode",
         )
         return (ws, num_splits) if partials else out
 
@@ -177,10 +187,13 @@ class HipAttnBackend(AttnBackend):
         """mla_decode(return_partials=True) + ops.mla_merge_absorb_uv_quant_fp8 in ONE launch (round 6,
         chitu_hip_mla_decode_merge_uv_quant_fp8): every split workgroup waits for its sequence's other splits and finishes one
         head -- merge, o . W_UV^T (model_deepseek_v3.py:697), act_quant of wo's input.  Bit-identical to the two launches.
-        Returns what the merge op returns, or None when the shape takes the two-launch form (one split, > 4096 groups)."""
+        Returns what the merge op returns, or None when the shape takes the two-launch form (one split, > 4096 groups, an
+        fp8 latent cache -- the fused launch reads bf16 rows only)."""
         from . import ops
 
         require_cuda(q_nope, q_pe, kv_cache, cache_seqlens_incl, block_table, w_uv, scale)
+        if is_fp8_mla_cache(kv_cache):
+            return None
         assert kv_cache.ndim == 3 and kv_cache.is_contiguous() and kv_cache.dtype == torch.bfloat16
         assert q_nope.dtype == torch.bfloat16 and q_pe.dtype == torch.bfloat16
         assert block_table.dtype == torch.int32 and cache_seqlens_incl.dtype == torch.int32
@@ -237,12 +250,16 @@ class HipAttnBackend(AttnBackend):
     ):
         """Same contract as TritonAttnBackend.mla_attn_with_kvcache (attn_backend.py:707-774):
         append this token's [kv_c | k_pe] row to its page, then attend over the sequence.
-        Returns [B, 1, H, kv_lora_rank]."""
+        Returns [B, 1, H, kv_lora_rank].  kv_cache uint8 [pages, page, 656] (the fp8 latent cache): the bf16 row `kv` is
+        quantised as it is appended (ops.append_mla_kv_fp8) and the fp8 decode kernel reads the pages."""
         assert window_size == (-1, -1) and softcap == 0.0, "not used by the MLA decode path"
         if softmax_scale is None:
             # the reference's default here is accidentally a 1-tuple (attn_backend.py:756-758)
             softmax_scale = 1.0 / ((self.qk_rope_head_dim + self.qk_nope_head_dim) ** 0.5)
-        append_to_paged_kv_cache(kv_cache, block_table, kv, cache_seqlens_excl_this_decode)
+        if is_fp8_mla_cache(kv_cache):
+            append_mla_kv_fp8(kv_cache, block_table, kv, cache_seqlens_excl_this_decode)
+        else:
+            append_to_paged_kv_cache(kv_cache, block_table, kv, cache_seqlens_excl_this_decode)
         B = q_nope.shape[0]
         o = self.mla_decode(q_nope, q_pe, kv_cache, cache_seqlens_incl_this_decode, block_table, float(softmax_scale))
         return o.view(B, 1, q_nope.shape[1], -1)

@@ -21,6 +21,21 @@ _MAX_SEQ_LEN = 2048
 _STAGE_RING = 4
 
 
+MLA_KV_CACHE_DTYPES = ("bf16", "fp8")
+
+
+def mla_kv_layout(kv_cache_dtype, kv_lora_rank=512, rope=64):
+    """(kv_shape_per_sample, dtype) of one cached MLA token, for PagedKVCacheManager(kv_shape_per_sample=..., dtype=...).
+    "bf16": [kv_norm(kv_c) | rope(k_pe)] as bf16.  "fp8": byte rows -- kv_lora_rank e4m3 codes, one fp32 power-of-two scale
+    per 128 latent channels, the rope part as bf16 (csrc/mla_kv_fp8.hip): 656 bytes for the 512 + 64 row, 0.569 of bf16's."""
+    if kv_cache_dtype == "bf16":
+        return (kv_lora_rank + rope,), torch.bfloat16
+    if kv_cache_dtype == "fp8":
+        assert kv_lora_rank % 128 == 0
+        return (kv_lora_rank + 4 * (kv_lora_rank // 128) + 2 * rope,), torch.uint8
+    raise ValueError(f"kv_cache_dtype must be one of {MLA_KV_CACHE_DTYPES}, got {kv_cache_dtype!r}")
+
+
 class PagedKVCacheManager:
     def __init__(
         self,

@@ -571,6 +571,12 @@ __global__ __launch_bounds__(128) void mla_merge_kernel(const bf16_t* __restrict
     *reinterpret_cast<i32x2*>(out + bh * kC + threadIdx.x * 4) = o2;
 }
 
+// The merge launch for the other producer of this workspace layout (mla_decode_kv_fp8.hip: a kernel is launched from the
+// translation unit that defines it).
+void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, int64_t rows, int num_splits, hipStream_t st) {
+    hipLaunchKernelGGL(mla_merge_kernel, dim3((unsigned)rows), dim3(128), 0, st, part_o, part_lse, out, num_splits);
+}
+
 }  // namespace chitu
 
 // Dynamic LDS of a decode workgroup; the opt-in above 64 KB is set on every call (it is per device and cheap; a process-wide

@@ -1,0 +1,345 @@
+// MLA (absorb mode) paged decode attention over the FP8 latent KV cache (new: no reference counterpart).
+//
+// chitu_hip_mla_decode's contract, grid, split logic and arithmetic (mla_decode.hip) with the cache holding 656-byte rows
+// (mla_kv_fp8.hip: 512 e4m3 codes | four power-of-two fp32 scales | 64 bf16 rope values): 0.569 of the bytes a bf16 row streams.
+// q stays bf16.  The latent is widened to bf16 as code * 2^e, which is exact, so the tile the MFMAs read holds the very bits
+// chitu_hip_mla_kv_dequant_fp8 would have written to a bf16 cache; QK^T, the online softmax, P -> bf16 and PV then run in
+// mla_decode_kernel's order and the output is bit-identical to chitu_hip_mla_decode on the dequantised cache at the same
+// num_splits (tests/test_gpu_mla_kv_fp8.py).
+//
+// How bytes move.  LDS holds ONE bf16 tile image (mla_decode.hip's: [64][1152 B], chunk c of row r at c ^ kv_swz(r)) and TWO
+// fp8 staging buffers [64][656 B] = 41 KiB each: 73.7 + 2 x 42.0 KB + P, the softmax exchange and the page ids = 158.75 KB of
+// the CU's 160.  (Two images do not fit beside a staging buffer.)  Per tile:
+//   wait for the tile's DMA | barrier | request the NEXT tile into the other staging buffer | widen staging -> image | barrier
+//   | multiply
+// so a tile's bytes are in flight while the previous tile is widened and multiplied, as in the bf16 kernel; the price of the
+// format is the widening pass (10 ds_read_b128 + 18 ds_write_b128 and ~300 VALU instructions per thread and tile) and one more
+// barrier per tile.
+//
+// Staging layout: the 41 16-byte chunks of a row back to back, rows back to back -- 2624 chunks = exactly 41 DMA pieces of
+// 1 KiB (lds_dma.h), piece n lane i = staging chunk 64 n + i = (row q / 41, chunk q % 41).  No swizzle.  The only reader is the
+// widening pass: 32 lanes take the 32 code chunks of one row (a ds_read_b128 group of 16 lanes reads chunks
+// of one row: 16 distinct slots of the 256-byte bank row wherever the row starts), 8 lanes the 8 rope chunks of one row (a
+// group spans 2 rows of 656 = 2 * 256 + 144 bytes: 2-way, 2 of the pass's 10 reads).  Its writes into the image are the side
+// that matters: code chunk p becomes image chunks 2 p and 2 p + 1, and the 16 lanes of a ds_write_b128 group hold 16 values of
+// p, i.e. only 8 distinct even slots.  So the lanes 16-31 and 48-63 store their ODD chunk first: every group then covers 16
+// distinct slots (the image's XOR swizzle permutes slots inside a row and keeps that).  Checked for every group, with the
+// coverage of the image, in tests/test_mla_kv_fp8_host.py.
+#include "common.h"
+#include "lds_dma.h"
+#include "mla_kv_fp8.h"
+
+namespace chitu {
+
+void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, int64_t rows, int num_splits, hipStream_t st);  // mla_decode.hip
+
+namespace kvfp8 {
+
+constexpr int kC = 512, kR = 64, kD = kC + kR, kTile = 64, kPStride = 72, kMaxTilesLds = 512;
+constexpr int kRowU = kD * 2;                    // 1152: a row of the bf16 image
+constexpr int kTileU = kTile * kRowU;            // 73728
+constexpr int kRowChunks = kKvFp8Row / 16;       // 41
+constexpr int kStageU = kTile * kKvFp8Row;       // 41984 = 41 pieces of 1 KiB
+constexpr int kStagePieces = kStageU / 1024;     // 41: wave w requests pieces w, w + 4, ...
+constexpr int kStageChunks = kStageU / 16;       // 2624
+constexpr int kStages = 2;                       // staging buffers: tile t + 1 lands while tile t is widened and multiplied
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+__device__ __forceinline__ int kv_swz(int r) { return ((r >> 3) & 1) * 5 + ((r >> 1) & 1) * 2; }
+
+// grid (num_splits, batch, heads/16); block 256
+__global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
+    const bf16_t* __restrict__ q_nope, int64_t qn_sb, int64_t qn_sh, const bf16_t* __restrict__ q_pe,
+    int64_t qp_sb, int64_t qp_sh, const uint8_t* __restrict__ cache, int64_t num_pages, int page_size,
+    const int32_t* __restrict__ block_table, int table_stride, const int32_t* __restrict__ seqlens,
+    float scale, bf16_t* __restrict__ part_o, float* __restrict__ part_lse, bf16_t* __restrict__ out,
+    int H, int num_splits) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint8_t* kv_lds = smem;                                               // [64][kRowU] the bf16 image
+    uint8_t* stage0 = smem + kTileU;                                      // [kStages][64][656] fp8 rows as they are cached
+    bf16_t* p_lds = reinterpret_cast<bf16_t*>(smem + kTileU + kStages * kStageU);   // [16][72]
+    float* red_max = reinterpret_cast<float*>(smem + kTileU + kStages * kStageU + 16 * kPStride * 2);  // [4][16]
+    float* red_sum = red_max + 64;                                        // [4][16]
+    int* pages_lds = reinterpret_cast<int*>(red_sum + 64);                // [kMaxTilesLds]
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 15, g = lane >> 4;
+    const int split = blockIdx.x, b = blockIdx.y, hb = blockIdx.z;
+    const int h0 = hb * 16;
+    const int32_t* tbl = block_table + (int64_t)b * table_stride;
+    const int max_page_idx = table_stride - 1;
+    const int L = max(seqlens[b], 0);  // a corrupt negative length is an empty sequence
+    const int n_tiles = (L + kTile - 1) / kTile;
+    const int tile0 = (int)((unsigned)n_tiles * (unsigned)split / (unsigned)num_splits);
+    const int tile1 = (int)((unsigned)n_tiles * (unsigned)(split + 1) / (unsigned)num_splits);
+    if (tile0 >= tile1) {  // an empty split publishes LSE = -inf and zero rows (nothing of it is read by the merge)
+        if (num_splits > 1) {
+            if (tid < 16 && h0 + tid < H) part_lse[((int64_t)b * H + h0 + tid) * num_splits + split] = -INFINITY;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int chunk = tid + i * 256, hr = chunk >> 6, c8 = chunk & 63;
+                if (h0 + hr < H)
+                    *reinterpret_cast<i32x4*>(part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8) = i32x4{0, 0, 0, 0};
+            }
+        } else {
+            for (int i = tid; i < 16 * kC / 8; i += 256)
+                if (h0 + (i >> 6) < H) *reinterpret_cast<i32x4*>(out + ((int64_t)b * H + h0 + (i >> 6)) * kC + (i & 63) * 8) = i32x4{0, 0, 0, 0};
+        }
+        return;
+    }
+    const bool pages_in_lds = (tile1 - tile0) <= kMaxTilesLds;
+    auto page_src = [&](int64_t page, int t0) -> const uint8_t* {
+        if (page < 0 || page >= num_pages) page = 0;  // corrupt table: stay in bounds
+        return cache + (page * page_size + (t0 % page_size)) * (int64_t)kKvFp8Row;
+    };
+    auto tile_src = [&](int tile) -> const uint8_t* {
+        const int t0 = tile * kTile;
+        return page_src(pages_in_lds && tile > tile0 ? pages_lds[tile - tile0] : tbl[min(t0 / page_size, max_page_idx)], t0);
+    };
+    // this wave's pieces of a tile: piece n = wave + 4 i (n < 41); lane's staging chunk 64 n + lane -> (row, byte offset in the row)
+    int prow[11];
+    uint32_t poff[11];
+#pragma unroll
+    for (int i = 0; i < 11; ++i) {
+        const int qi = min(64 * (wave + 4 * i) + lane, kStageChunks - 1);
+        prow[i] = qi / kRowChunks;
+        poff[i] = (uint32_t)((qi % kRowChunks) << 4);
+    }
+    const uint32_t lds_stage = lds_offset_of(stage0);
+    // rows past the sequence end re-read the tile's last valid row: finite, and their probabilities are exactly 0
+    auto issue = [&](const uint8_t* src, int valid, int buf) {
+        const uint8_t* sb = uniform_ptr(src);
+#pragma unroll
+        for (int i = 0; i < 11; ++i)
+            if (wave + 4 * i < kStagePieces)
+                glds16_sbase<true>(sb, (uint32_t)(min(prow[i], valid - 1) * kKvFp8Row) + poff[i], lds_stage + (uint32_t)(buf * kStageU + (wave + 4 * i) * 1024));
+    };
+    issue(tile_src(tile0), min(kTile, L - tile0 * kTile), 0);
+    {   // Q (16 heads x 576): 1152 chunks of 16 B, <= 5 per thread, coalesced, into the image's own layout (row = head, chunk c
+        // at c ^ swz(row)); every wave then reads all of it back like a K fragment: the A operand lives in registers
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int c = tid + i * 256;
+            if (c < 16 * 72) {
+                const int row = c / 72, col = c % 72;
+                const int h = min(h0 + row, H - 1);
+                const bf16_t* src = col < 64 ? q_nope + b * qn_sb + h * qn_sh + col * 8 : q_pe + b * qp_sb + h * qp_sh + (col - 64) * 8;
+                *reinterpret_cast<i32x4*>(kv_lds + row * kRowU + ((col ^ kv_swz(row)) << 4)) = *reinterpret_cast<const i32x4*>(src);
+            }
+        }
+    }
+    if (pages_in_lds && tile1 - tile0 > 1) {  // page ids of the following tiles
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (tid + i * 256 < tile1 - tile0)
+                pages_lds[tid + i * 256] = tbl[min(((tile0 + tid + i * 256) * kTile) / page_size, max_page_idx)];
+    }
+
+    f32x4 o[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run[4], l_run[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        m_run[r] = -INFINITY;
+        l_run[r] = 0.f;
+    }
+    // fragment addressing inside the image (mla_decode.hip's)
+    const int ksw = kv_swz(j);
+    const int koff0 = (wave * 16 + j) * kRowU + ((g ^ ksw) << 4);
+    const int koff1 = (wave * 16 + j) * kRowU + (((g ^ ksw) ^ 4) << 4);
+    const int vsw = (g & 1) * 5 + ((j >> 3) & 1) * 2;
+    const int vrow_off = (g * 8 + (j >> 2)) * kRowU + wave * 256 + ((((j >> 1) & 1) ^ (vsw & 1)) << 4) + (j & 1) * 8;
+    int vx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) vx[k] = ((2 * k) ^ (vsw & 6)) << 4;
+    // the widening pass: which of its two image chunks a lane stores first (see the layout note above)
+    const int odd_first = (lane >> 4) & 1;
+
+    __syncthreads();  // Q and the page list are visible
+    s16x8 qf[18];     // lane (j, g): elements [32 kk + 8 g, +8) of head j
+#pragma unroll
+    for (int kk = 0; kk < 18; ++kk)
+        qf[kk] = *reinterpret_cast<const s16x8*>(kv_lds + j * kRowU + (kk >> 1) * 128 + (((g + 4 * (kk & 1)) ^ ksw) << 4));
+
+    for (int tile = tile0; tile < tile1; ++tile) {
+        const int valid = min(kTile, L - tile * kTile);
+        const int buf = (tile - tile0) & (kStages - 1);
+        glds_wait_all();   // this wave's pieces of the tile
+        __syncthreads();   // everyone's; the image (Q, or the previous tile), the other staging buffer (widened one tile ago)
+                           // and the softmax exchange areas are free
+        if (tile + 1 < tile1) issue(tile_src(tile + 1), min(kTile, L - (tile + 1) * kTile), buf ^ 1);
+        const uint8_t* stage = stage0 + buf * kStageU;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {  // the codes: chunk p (16 codes) of row r -> image chunks 2 p, 2 p + 1; 32 lanes per row
+            const int c = tid + i * 256, row = c >> 5, pos = c & 31;
+            const uint8_t* srow = stage + row * kKvFp8Row;
+            const i32x4 raw = *reinterpret_cast<const i32x4*>(srow + pos * 16);
+            const float s = *reinterpret_cast<const float*>(srow + kKvFp8ScaleOff + (pos >> 3) * 4);
+            // (the halves are exchanged as codes, 4 selects, not as bf16, 8)
+            const i32x4 first = kv_fp8_widen8((uint32_t)(odd_first ? raw[2] : raw[0]), (uint32_t)(odd_first ? raw[3] : raw[1]), s);
+            const i32x4 second = kv_fp8_widen8((uint32_t)(odd_first ? raw[0] : raw[2]), (uint32_t)(odd_first ? raw[1] : raw[3]), s);
+            uint8_t* img = kv_lds + row * kRowU;
+            const int sw = kv_swz(row);
+            *reinterpret_cast<i32x4*>(img + (((2 * pos + odd_first) ^ sw) << 4)) = first;
+            *reinterpret_cast<i32x4*>(img + (((2 * pos + 1 - odd_first) ^ sw) << 4)) = second;
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {  // the rope part: 8 chunks of a row, copied to image chunks 64 .. 71
+            const int c = tid + i * 256, row = c >> 3, pos = c & 7;
+            *reinterpret_cast<i32x4*>(kv_lds + row * kRowU + (((64 + pos) ^ kv_swz(row)) << 4)) =
+                *reinterpret_cast<const i32x4*>(stage + row * kKvFp8Row + kKvFp8RopeOff + pos * 16);
+        }
+        __syncthreads();   // the image is complete
+        const uint8_t* kv = kv_lds;
+
+        // ---- S = Q K^T for this wave's 16 tokens (two accumulators: no 18-deep dependent chain)
+        f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < 18; kk += 2) {
+            const s16x8 k0 = *reinterpret_cast<const s16x8*>(kv + koff0 + (kk >> 1) * 128);
+            const s16x8 k1 = *reinterpret_cast<const s16x8*>(kv + koff1 + (kk >> 1) * 128);
+            s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk], k0, s0, 0, 0, 0);
+            s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk + 1], k1, s1, 0, 0, 0);
+        }
+        // lane holds S[head 4g+r][token wave*16+j]
+        const bool tok_ok = (wave * 16 + j) < valid;
+        float sv[4], mx[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            sv[r] = tok_ok ? (s0[r] + s1[r]) * scale : -INFINITY;
+            mx[r] = row16_reduce_max(sv[r]);
+        }
+        if (j == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red_max[wave * 16 + g * 4 + r] = mx[r];
+        }
+        __syncthreads();
+        float alpha[4], psum[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int hh = g * 4 + r;
+            const float mt = __builtin_fmaxf(__builtin_fmaxf(red_max[hh], red_max[16 + hh]),
+                                             __builtin_fmaxf(red_max[32 + hh], red_max[48 + hh]));
+            const float m_new = __builtin_fmaxf(m_run[r], mt);  // finite: the tile's first token is valid
+            alpha[r] = __expf(m_run[r] - m_new);
+            m_run[r] = m_new;
+            const float p = __expf(sv[r] - m_new);
+            psum[r] = row16_reduce_sum(p);
+            p_lds[hh * kPStride + wave * 16 + j] = f32_to_bf16(p);
+        }
+        if (j == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red_sum[wave * 16 + g * 4 + r] = psum[r];
+        }
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) o[c][r] *= alpha[r];
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int hh = g * 4 + r;
+            l_run[r] = l_run[r] * alpha[r] + (red_sum[hh] + red_sum[16 + hh] + red_sum[32 + hh] + red_sum[48 + hh]);
+        }
+
+        // ---- O += P V : this wave owns latent columns [wave*128, wave*128+128)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const s16x8 pfrag = *reinterpret_cast<const s16x8*>(p_lds + j * kPStride + ks * 32 + g * 8);
+            const uint8_t* vbase = kv + vrow_off + ks * 32 * kRowU;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const uint8_t* va = vbase + vx[c & 3] + (c >> 2) * 128;
+                const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va));
+                const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va + 4 * kRowU));
+                s16x8 vf;
+                vf[0] = v0[0]; vf[1] = v0[1]; vf[2] = v0[2]; vf[3] = v0[3];
+                vf[4] = v1[0]; vf[5] = v1[1]; vf[6] = v1[2]; vf[7] = v1[3];
+                o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, vf, o[c], 0, 0, 0);
+            }
+        }
+    }
+
+    // ---- epilogue: lane holds O[head 4g+r][col wave*128 + c*16 + j]
+    if (num_splits == 1) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int h = h0 + g * 4 + r;
+            if (h >= H) continue;
+            const float inv = 1.0f / l_run[r];
+            bf16_t* dst = out + ((int64_t)b * H + h) * kC + wave * 128 + j;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) dst[c * 16] = f32_to_bf16(o[c][r] * inv);
+        }
+        return;
+    }
+    // split partials: transposed through LDS (the image is dead) so every thread stores 16-B pieces of whole rows: bf16
+    // normalised rows + the fp32 LSE, the workspace layout mla_merge_kernel and mla_merge_uv_quant_kernel read
+    __syncthreads();
+    bf16_t* o_lds = reinterpret_cast<bf16_t*>(kv_lds);  // [16][512] bf16 = 16 KB
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float inv = 1.0f / l_run[r];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) o_lds[(g * 4 + r) * kC + wave * 128 + c * 16 + j] = f32_to_bf16(o[c][r] * inv);
+        const int h = h0 + g * 4 + r;
+        if (wave == 0 && j == 0 && h < H) part_lse[((int64_t)b * H + h) * num_splits + split] = m_run[r] + __logf(l_run[r]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int chunk = tid + i * 256;
+        const int hr = chunk >> 6, c8 = chunk & 63;
+        if (h0 + hr < H) {
+            const i32x4 v = *reinterpret_cast<const i32x4*>(o_lds + hr * kC + c8 * 8);
+            bf16_t* dst = part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8;
+            // write-through (sc1), as in mla_decode.hip: the partials stream out instead of waiting dirty for the end-of-kernel release
+            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+        }
+    }
+}
+
+}  // namespace kvfp8
+}  // namespace chitu
+
+extern "C" int chitu_hip_mla_decode_kv_fp8(const void* q_nope, int64_t qn_stride_b, int64_t qn_stride_h,
+                                           const void* q_pe, int64_t qp_stride_b, int64_t qp_stride_h,
+                                           const void* kv_cache, int64_t num_pages, int32_t page_size,
+                                           const int32_t* block_table, int32_t table_stride,
+                                           const int32_t* seqlens, float softmax_scale, void* out_bf16,
+                                           int32_t batch, int32_t heads, int32_t kv_lora_rank,
+                                           int32_t rope_dim, int32_t num_splits, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+    using namespace chitu;
+    using namespace chitu::kvfp8;
+    CHITU_REQUIRE(q_nope && q_pe && kv_cache && block_table && seqlens);
+    CHITU_REQUIRE(out_bf16 || num_splits > 1);  // no out: leave the split partials for a fused consumer
+    CHITU_REQUIRE(batch >= 0 && heads >= 1 && num_pages >= 1 && table_stride >= 1);
+    CHITU_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)q_nope & 15) == 0 && ((uintptr_t)q_pe & 15) == 0);  // 16-byte loads
+    if (kv_lora_rank != kC || rope_dim != kR) return CHITU_ERR_UNSUPPORTED;
+    if (page_size < kTile || page_size % kTile != 0) return CHITU_ERR_UNSUPPORTED;
+    CHITU_REQUIRE(num_splits >= 1 && num_splits <= 256);
+    // the kernel's split arithmetic is 32-bit: tiles the table can address x (splits + 1) must stay below 2^31
+    CHITU_REQUIRE((int64_t)table_stride * (page_size / kTile) * (num_splits + 1) < (1ll << 31));
+    if (batch == 0) return CHITU_OK;
+    bf16_t* part_o = nullptr;
+    float* part_lse = nullptr;
+    if (num_splits > 1) {
+        // workspace: bf16 partial rows [batch, heads, splits, 512] | fp32 LSE [batch, heads, splits]
+        const int64_t need = (int64_t)batch * heads * num_splits * (kC * 2 + 4);
+        CHITU_REQUIRE(workspace && workspace_bytes >= need);
+        part_o = (bf16_t*)workspace;
+        part_lse = (float*)(part_o + (int64_t)batch * heads * num_splits * kC);
+    }
+    hipStream_t st = (hipStream_t)stream;
+    // the opt-in above 64 KB of dynamic LDS is set on every call (per device and cheap, as in mla_decode.hip)
+    const size_t lds = kTileU + kStages * kStageU + 16 * kPStride * 2 + 2 * 64 * sizeof(float) + kMaxTilesLds * sizeof(int);
+    (void)hipFuncSetAttribute((const void*)mla_decode_kv_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const dim3 grid((unsigned)num_splits, (unsigned)batch, (unsigned)((heads + 15) / 16));
+    hipLaunchKernelGGL(mla_decode_kv_fp8_kernel, grid, dim3(256), lds, st, (const bf16_t*)q_nope, qn_stride_b, qn_stride_h,
+                       (const bf16_t*)q_pe, qp_stride_b, qp_stride_h, (const uint8_t*)kv_cache, num_pages, (int)page_size,
+                       block_table, (int)table_stride, seqlens, softmax_scale, part_o, part_lse, (bf16_t*)out_bf16, (int)heads,
+                       (int)num_splits);
+    if (num_splits > 1 && out_bf16) launch_mla_merge(part_o, part_lse, (bf16_t*)out_bf16, (int64_t)batch * heads, (int)num_splits, st);
+    CHITU_RETURN_LAUNCH_STATUS();
+}

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 from . import fused_moe, graphs, ops
 from . import tensor_parallel as tp
 from .attn_backend import HipAttnBackend
-from .cache_manager import PagedKVCacheManager
+from .cache_manager import PagedKVCacheManager, mla_kv_layout
 
 FP8 = torch.float8_e4m3fn
 BLOCK = 128
@@ -72,6 +72,10 @@ class DeepSeekV3Args:
     # Storage of the routed (and, without expert parallelism, the stacked shared) experts: "fp8" = e4m3 + [128,128] block
     # scales (the reference's), "mxfp4" = OCP MXFP4, packed e2m1 + one E8M0 byte per 32 k (W4A8: fused_experts(use_mxfp4_w4a8)).
     expert_dtype: str = "fp8"
+    # Format of the paged latent KV cache: "bf16" = [kv_norm(kv_c) | rope(k_pe)] rows of 576 bf16 (the reference's), "fp8" =
+    # 656-byte rows, the latent as e4m3 with one power-of-two scale per 128 channels, the rope part bf16 (0.569 of the bytes;
+    # csrc/mla_kv_fp8.hip).  The cache handed to the decoder is built from cache_manager.mla_kv_layout(kv_cache_dtype).
+    kv_cache_dtype: str = "bf16"
 
     def tp_degree(self):
         return self.shard_degree if self.shard_degree is not None else tp.get_tp_size()
@@ -199,11 +203,30 @@ def _wqkv_a_splits(bs: int, n: int, k: int) -> int:
     return 2 if tiles <= 160 else 1
 
 
+class Fp8KvStage:
+    """The decode step's KV row on its way into an fp8 latent cache.  The launches that produce the row (ops.mla_q_proj,
+    ops.mla_qkv_post, ops.absorb_bmm_rope_kv_fp8) append bf16 rows to a paged cache; with an fp8 cache they are pointed at
+    this one instead -- one row per sequence, page size 1, table = arange, lengths = 0, so sequence b's row lands in row b --
+    and ops.append_mla_kv_fp8 then quantises it into the real page.  One more small launch per layer; the row every
+    producer path leaves in the page is, bit for bit, the quantiser's image of the row it would have left in a bf16 cache.
+    Allocated once (at construction of the decoder): a captured graph sees fixed addresses.  Shared by all layers: they
+    run in turn on one stream."""
+
+    def __init__(self, max_bs, device):
+        self.rows = torch.zeros(max_bs, 1, 576, dtype=torch.bfloat16, device=device)
+        self.table = torch.arange(max_bs, dtype=torch.int32, device=device).view(max_bs, 1)
+        self.lens = torch.zeros(max_bs, dtype=torch.int32, device=device)
+
+
 class AttentionDeepSeekV3(torch.nn.Module):
     """MLA, absorb-without-precomp, paged decode (model_deepseek_v3.py:394-703)."""
 
-    def __init__(self, args: DeepSeekV3Args, layer_id, cache, attn_backend, device=None):
+    def __init__(self, args: DeepSeekV3Args, layer_id, cache, attn_backend, device=None, kv_stage: Optional[Fp8KvStage] = None):
         super().__init__()
+        self.kv_fp8 = args.kv_cache_dtype == "fp8"
+        self.kv_stage = kv_stage
+        if self.kv_fp8 and kv_stage is None and cache is not None:
+            self.kv_stage = Fp8KvStage(cache.curr_seq_lens_gpu_excl_this_decode.shape[0], cache.device)
         tp_size = args.tp_degree()
         self.layer_id, self.cache, self.attn_backend = layer_id, cache, attn_backend
         self.dim = args.dim
@@ -263,7 +286,7 @@ class AttentionDeepSeekV3(torch.nn.Module):
         6 launches (the reference's decode_forward_paged + _run_linear issue ~25): wqkv_a GEMM,
         [q_norm + quant -> wq_b GEMM | kv_norm + RoPE(k_pe) + page append], [W_UK absorb | RoPE(q_pe)],
         MLA decode, [split merge + W_UV absorb + quant], wo GEMM.  (7 with batches above 16: the q_norm / kv
-        launch and the wq_b GEMM apart.)"""
+        launch and the wq_b GEMM apart.)  kv_cache_dtype "fp8": one more, the quantising append (Fp8KvStage)."""
         H, C, R = self.n_local_heads, self.kv_lora_rank, self.qk_rope_head_dim
         if first is not None:
             bs = first.shape[0]
@@ -271,6 +294,11 @@ class AttentionDeepSeekV3(torch.nn.Module):
             bs = x_quant[0].rows if isinstance(x_quant[0], ops.TiledQuant) else x_quant[0].shape[0]
         cache = self.cache
         kv_cache = cache.get_paged_kv_cache(self.layer_id)
+        kv_table, kv_lens = cache.get_gpu_block_table(), cache.get_gpu_seq_lens_excl_this_decode()
+        paged = None
+        if self.kv_fp8:  # the producers below write this step's bf16 rows to the stage; moved into the pages behind them
+            paged = (kv_cache, kv_table, kv_lens)
+            kv_cache, kv_table, kv_lens = self.kv_stage.rows, self.kv_stage.table[:bs], self.kv_stage.lens[:bs]
         nblk = C // BLOCK
         if self.q_lora_rank > 0:
             # wqkv_a: [bs, q_lora + C + R] (optionally as split-K planes, see _wqkv_a_splits)
@@ -288,13 +316,11 @@ class AttentionDeepSeekV3(torch.nn.Module):
                 # [kv_norm(kv_c) | rope(k_pe)] row straight into its page on extra workgroups of the same grid
                 q = ops.mla_q_proj(q_a_kv, self.q_lora_rank, self.q_norm.weight, self.q_norm.eps, self.wq_b.weight,
                                    self.wq_b.scale, self.kv_norm.weight, self.kv_norm.eps, cos, sin, kv_cache,
-                                   cache.get_gpu_block_table(), cache.get_gpu_seq_lens_excl_this_decode(),
-                                   out_dtype=torch.bfloat16)
+                                   kv_table, kv_lens, out_dtype=torch.bfloat16)
             else:
                 # q_norm + quant, and this token's [kv_norm(kv_c) | rope(k_pe)] row straight into its page
                 qq, qs = ops.mla_qkv_post(q_a_kv, self.q_lora_rank, self.q_norm.weight, self.q_norm.eps, self.kv_norm.weight,
-                                          self.kv_norm.eps, cos, sin, kv_cache, cache.get_gpu_block_table(),
-                                          cache.get_gpu_seq_lens_excl_this_decode())
+                                          self.kv_norm.eps, cos, sin, kv_cache, kv_table, kv_lens)
                 q = self.wq_b(None, x_quant=(qq, qs))
             q = q.view(bs, H, self.qk_head_dim)
             q_nope, q_pe = q[..., : self.qk_nope_head_dim], q[..., self.qk_nope_head_dim :]
@@ -309,7 +335,10 @@ class AttentionDeepSeekV3(torch.nn.Module):
             # ONE launch: W_UK absorb, RoPE(q_pe) in place, and this token's [kv_norm(kv_c) | rope(k_pe)] row into its page
             q_abs = ops.absorb_bmm_rope_kv_fp8(q_nope, self.w_uk_transposed(), self.wkv_b.scale, 0, 2 * nblk, 1, 0, q_pe, cos, sin,
                                                q_kv[:, nq:], self.kv_norm.weight, self.kv_norm.eps, kv_cache,
-                                               cache.get_gpu_block_table(), cache.get_gpu_seq_lens_excl_this_decode())
+                                               kv_table, kv_lens)
+        if paged is not None:
+            kv_cache = paged[0]
+            ops.append_mla_kv_fp8(kv_cache, paged[1], self.kv_stage.rows[:bs], paged[2])
         # small batches: the split-KV merge runs inside the W_UV projection kernel (CHITU_MLA_FUSED_TAIL=1: both inside the
         # decode launch, same bits, measured slower -- see _MLA_FUSED_TAIL)
         fuse_merge = bs <= 32 and C == 512
@@ -337,7 +366,10 @@ class AttentionDeepSeekV3(torch.nn.Module):
         """Prefill in absorb mode (model_deepseek_v3.py:538-603): the same projections as decode on all
         T prompt tokens, [kv_norm(kv_c) | rope(k_pe)] rows written to the pages by the cache manager
         (cache_manager.py:93-142), causal MQA through attn_backend.attn_varlen_func.  Op-level launches
-        (prefill is outside the decode hot path; SURVEY 8f.1 first cut)."""
+        (prefill is outside the decode hot path; SURVEY 8f.1 first cut).
+        kv_cache_dtype "fp8": the rows are quantised (ops.mla_kv_quant_fp8) on their way into the pages; the prompt's own
+        attention below keeps reading the unquantised rows, as other engines with an fp8 KV cache do -- only later decode
+        steps see the quantised prompt."""
         H, C, R = self.n_local_heads, self.kv_lora_rank, self.qk_rope_head_dim
         T = x_quant[0].shape[0]
         if self.q_lora_rank > 0:
@@ -353,7 +385,8 @@ class AttentionDeepSeekV3(torch.nn.Module):
         kv_c = ops.rms_norm(q_a_kv[:, ql : ql + C], self.kv_norm.weight, self.kv_norm.eps)
         q_pe, k_pe = ops.apply_rotary_pos_emb(q_pe, q_a_kv[:, ql + C :], cos, sin, rotary_type="llama")
         kv_pe = torch.cat([kv_c, k_pe], dim=-1)  # [T, C + R]
-        self.cache.finalize_cache_bylayer_prefill(kv_pe, None, self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
+        self.cache.finalize_cache_bylayer_prefill(ops.mla_kv_quant_fp8(kv_pe) if self.kv_fp8 else kv_pe, None,
+                                                  self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
         nblk = C // BLOCK
         q_abs = ops.absorb_bmm_fp8(q_nope, self.w_uk_transposed(), self.wkv_b.scale, 0, 2 * nblk, 1, 0)
         o = self.attn_backend.attn_varlen_func(
@@ -507,9 +540,9 @@ class MoEDeepSeekV3(torch.nn.Module):
 class TransformerBlockDeepSeekV3(torch.nn.Module):
     """x += attn(attn_norm(x)); x += ffn(ffn_norm(x))  (model_deepseek_v3.py:1064-1114)."""
 
-    def __init__(self, layer_id, args, cache, attn_backend, device=None):
+    def __init__(self, layer_id, args, cache, attn_backend, device=None, kv_stage=None):
         super().__init__()
-        self.attn = AttentionDeepSeekV3(args, layer_id, cache, attn_backend, device)
+        self.attn = AttentionDeepSeekV3(args, layer_id, cache, attn_backend, device, kv_stage)
         self.is_moe = layer_id >= args.n_dense_layers
         self.ffn = MoEDeepSeekV3(args, device) if self.is_moe else MLPDeepSeekV3(args, device)
         self.attn_norm = RMSNormW(args.dim, args.norm_eps, device)
@@ -601,7 +634,18 @@ class DeepSeekV3Decoder(torch.nn.Module):
         # (model_deepseek_v3.py:1292-1319), sharded `deg` ways
         self.embed_weight = torch.nn.Parameter(torch.empty(self.vocab_local, args.dim, dtype=torch.bfloat16, device=device), requires_grad=False)
         ids = list(range(args.n_layers)) if layers is None else layers
-        self.layers = torch.nn.ModuleList(TransformerBlockDeepSeekV3(i, args, cache, attn_backend, device) for i in ids)
+        kv_shape, kv_dtype = mla_kv_layout(args.kv_cache_dtype, args.kv_lora_rank, args.qk_rope_head_dim)  # (raises on an unknown name)
+        kv_stage = None
+        assert args.kv_cache_dtype == "bf16" or (args.kv_lora_rank, args.qk_rope_head_dim) == (512, 64), "the fp8 KV kernels are built for 512 + 64 rows"
+        if cache is not None:
+            held = getattr(cache, "paged_kv_cache", None)
+            matches = held is not None and held.dtype == kv_dtype and tuple(held.shape[3:]) == tuple(kv_shape)
+            assert matches or (held is None and args.kv_cache_dtype == "bf16"), (
+                f"kv_cache_dtype={args.kv_cache_dtype!r} needs a cache of {kv_shape} x {kv_dtype} per token "
+                f"(cache_manager.mla_kv_layout), got {None if held is None else (tuple(held.shape[3:]), held.dtype)}")
+            if args.kv_cache_dtype == "fp8":
+                kv_stage = Fp8KvStage(cache.curr_seq_lens_gpu_excl_this_decode.shape[0], device)
+        self.layers = torch.nn.ModuleList(TransformerBlockDeepSeekV3(i, args, cache, attn_backend, device, kv_stage) for i in ids)
         self.norm = RMSNormW(args.dim, args.norm_eps, device)
         self.head_weight = torch.nn.Parameter(torch.empty(self.vocab_local, args.dim, dtype=torch.bfloat16, device=device), requires_grad=False)
         cos, sin = precompute_freqs_cis(args, max_position_embeddings)

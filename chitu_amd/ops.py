@@ -229,6 +229,64 @@ def append_to_paged_kv_cache(kv_cache, page_table, this_kv, old_seq_lens):
     )
 
 
+MLA_KV_FP8_ROW = 656  # bytes of one token of the fp8 latent KV cache (csrc/mla_kv_fp8.hip; cache_manager.mla_kv_layout("fp8"))
+
+
+def _rows576(x):
+    """bf16 [T, 576] rows the fp8 KV kernels can read in place: unit inner stride, row stride a multiple of 8 elements,
+    16-byte aligned (a [:, q:q+576] view of a projection's output is); anything else is copied."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 2 and x.shape[1] == 576
+    ok = x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= 576 and x.data_ptr() % 16 == 0
+    return x if ok or x.shape[0] == 0 else x.contiguous()
+
+
+def mla_kv_quant_fp8(kv, out=None):
+    """bf16 [T, 576] rows [kv_norm(kv_c) | rope(k_pe)] (row-strided views allowed) -> uint8 [T, 656] rows of the fp8 latent
+    KV cache: 512 e4m3 codes | 4 fp32 power-of-two scales (one per 128 channels) | the 64 rope values as bf16.
+    out: a uint8 [T, >= 656] destination with a row stride that is a multiple of 16 bytes; columns beyond 656 are left alone."""
+    require_cuda(kv, out)
+    kv = _rows576(kv)
+    T = kv.shape[0]
+    if out is None:
+        out = torch.empty(T, MLA_KV_FP8_ROW, dtype=torch.uint8, device=kv.device)
+    assert out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == T and out.shape[1] >= MLA_KV_FP8_ROW and out.stride(1) == 1
+    check(_lib.lib().chitu_hip_mla_kv_quant_fp8(ptr(kv), i64(kv.stride(0)), ptr(out), i64(out.stride(0)), i64(T), stream_ptr()),
+          "mla_kv_quant_fp8")
+    return out
+
+
+def mla_kv_dequant_fp8(rows):
+    """The inverse of mla_kv_quant_fp8: uint8 [..., 656] rows (a whole cache included) -> bf16 [..., 576].  Exact: every
+    code x scale product is a bf16 number."""
+    require_cuda(rows)
+    assert rows.dtype == torch.uint8 and rows.shape[-1] == MLA_KV_FP8_ROW and rows.is_contiguous()
+    T = rows.numel() // MLA_KV_FP8_ROW
+    out = torch.empty(*rows.shape[:-1], 576, dtype=torch.bfloat16, device=rows.device)
+    check(_lib.lib().chitu_hip_mla_kv_dequant_fp8(ptr(rows), i64(MLA_KV_FP8_ROW), ptr(out), i64(T), stream_ptr()),
+          "mla_kv_dequant_fp8")
+    return out
+
+
+def append_mla_kv_fp8(kv_cache, page_table, this_kv, old_seq_lens):
+    """append_to_paged_kv_cache for the fp8 latent cache: row i of this_kv (bf16 [bs, 576] or [bs, 1, 576]) is quantised
+    (mla_kv_quant_fp8's bytes) into kv_cache[page_table[i][L_i // page]][L_i % page], kv_cache uint8 [pages, page, 656].
+    An out-of-range table entry, a negative length or a position beyond the table writes nothing."""
+    require_cuda(kv_cache, page_table, this_kv, old_seq_lens)
+    assert kv_cache.dtype == torch.uint8 and kv_cache.dim() == 3 and kv_cache.shape[-1] == MLA_KV_FP8_ROW and kv_cache.is_contiguous()
+    assert page_table.dtype == torch.int32 and old_seq_lens.dtype == torch.int32
+    assert page_table.dim() == 2 and page_table.is_contiguous() and old_seq_lens.is_contiguous()
+    bs = page_table.shape[0]
+    assert old_seq_lens.shape[0] == bs and this_kv.shape[0] == bs
+    src = _rows576(this_kv.reshape(bs, 576) if this_kv.dim() == 3 else this_kv)
+    check(
+        _lib.lib().chitu_hip_mla_kv_append_fp8(
+            ptr(src), i64(src.stride(0)), ptr(kv_cache), i64(kv_cache.shape[0]), i32(kv_cache.shape[1]), ptr(page_table),
+            i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), stream_ptr(),
+        ),
+        "append_mla_kv_fp8",
+    )
+
+
 def apply_rotary_pos_emb_torch(q, k, cos, sin, rotary_type="hf-llama"):
     """Name kept for source compatibility with chitu/ops.py:243-308; runs the HIP kernel."""
     return apply_rotary_pos_emb(q, k, cos, sin, rotary_type=rotary_type)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 5  /* 5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 6  /* 6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -458,6 +458,39 @@ int chitu_hip_mla_decode(const void* q_nope, int64_t qn_stride_b, int64_t qn_str
                          float softmax_scale, void* out_bf16, int32_t batch, int32_t heads,
                          int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits,
                          void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- FP8 latent KV cache of the MLA paged decode (csrc/mla_kv_fp8.hip, csrc/mla_decode_kv_fp8.hip) --------
+ * One cached token is 656 bytes: [0, 512) kv_norm(kv_c) as 512 OCP e4m3fn codes | [512, 528) four fp32 scales, one per 128
+ * latent channels, each an exact power of two | [528, 656) rope(k_pe), 64 bf16, copied unchanged.  Per group: amax = max|x|,
+ * e = the smallest integer with amax <= 448 * 2^e clamped to e >= -64 (amax == 0: -64), scale = 2^e, code = RNE_e4m3(x * 2^-e)
+ * (never overflows); NaN / Inf inputs are unspecified.  code * scale is exactly representable in bf16: dequantisation is exact.
+ * A layer's cache is uint8 [num_pages, page_size, 656], base 16-byte aligned.
+ *   chitu_hip_mla_kv_quant_fp8    new: no reference counterpart.  src bf16 [rows, 576] with a row stride in elements (% 8,
+ *     base 16-byte aligned) -> dst bytes [rows, 656] with a row stride in bytes (>= 656, % 16, base 16-byte aligned); bytes
+ *     of a destination row beyond 656 are not written.
+ *   chitu_hip_mla_kv_dequant_fp8  new: no reference counterpart.  The inverse: byte rows (stride as above) -> bf16 [rows, 576]
+ *     contiguous.  Exact.
+ *   chitu_hip_mla_kv_append_fp8   new: no reference counterpart.  Quantises row b of src bf16 [batch, 576] (row stride in
+ *     elements) into position old_seq_lens[b] of sequence b's page: cache[table[b][L / page_size]][L % page_size].  Any
+ *     page_size >= 1.  A table entry outside [0, num_pages), a negative length or a position beyond pages_per_seq writes nothing.
+ *   chitu_hip_mla_decode_kv_fp8   new: no reference counterpart.  chitu_hip_mla_decode's argument list and contract with
+ *     kv_cache reading 656-byte rows (page_size % 64 == 0; 159 KB of LDS).  q stays bf16; the latent is widened to bf16 in LDS
+ *     (exact) and everything behind that is chitu_hip_mla_decode's arithmetic in its order: the output, and with num_splits > 1
+ *     the workspace (same layout, same consumers), are bit-identical to chitu_hip_mla_decode on the dequantised cache. */
+int chitu_hip_mla_kv_quant_fp8(const void* src_bf16, int64_t src_stride, void* dst_u8, int64_t dst_stride_bytes,
+                               int64_t rows, void* stream);
+int chitu_hip_mla_kv_dequant_fp8(const void* src_u8, int64_t src_stride_bytes, void* dst_bf16, int64_t rows,
+                                 void* stream);
+int chitu_hip_mla_kv_append_fp8(const void* src_bf16, int64_t src_stride, void* kv_cache_u8, int64_t num_pages,
+                                int32_t page_size, const int32_t* block_table, int32_t pages_per_seq,
+                                const int32_t* old_seq_lens, int32_t batch, void* stream);
+int chitu_hip_mla_decode_kv_fp8(const void* q_nope, int64_t qn_stride_b, int64_t qn_stride_h,
+                                const void* q_pe, int64_t qp_stride_b, int64_t qp_stride_h,
+                                const void* kv_cache, int64_t num_pages, int32_t page_size,
+                                const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                                float softmax_scale, void* out_bf16, int32_t batch, int32_t heads,
+                                int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits,
+                                void* workspace, int64_t workspace_bytes, void* stream);
 
 /* MLA absorb-mode causal prefill attention (MQA, head dims 576 / 512): the attn_varlen_func call of
  * AttentionDeepSeekV3.prefill_forward (chitu/models/model_deepseek_v3.py:589-599; chitu/attn_backend.py:39-90).
