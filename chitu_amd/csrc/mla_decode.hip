@@ -20,17 +20,9 @@
 // the device-side sequence length, empty splits publish LSE = -inf.  Stage 2 merges splits.
 #include "common.h"
 #include "lds_dma.h"
+#include "mla_decode_tile.h"
 
 namespace chitu {
-
-constexpr int kC = 512;        // kv_lora_rank (latent / V width)
-constexpr int kR = 64;         // qk_rope_head_dim
-constexpr int kD = kC + kR;    // cached row width (576)
-constexpr int kTile = 64;      // KV tokens per tile
-constexpr int kPStride = 72;   // P row stride in bf16 elements (64 + 8 pad)
-constexpr int kMaxTilesLds = 512;  // page ids cached in LDS per split (32k tokens)
-
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 // grid (num_splits, batch, heads/16); block 256, one workgroup per CU (152 KB LDS).
 //
@@ -44,16 +36,8 @@ typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 // resident lines it cost 0.55 us per launch in the step (same-box kernel trace, profiles/r05_ab_mla_decode_dma.txt:
 // register-staged 13.29 us, DMA 12.07, DMA + nt 11.52; ctx 8192: 36.1 -> 27.1 us).
 //
-// LDS image of a tile: [64 rows][1152 B] unpadded, the 16-byte chunk c of row r stored at c ^ swz(r),
-// swz(r) = 5 * bit3(r) + 2 * bit1(r).  A DMA piece is 1 KiB of the image, lane-linear (lds_dma.h): image chunk q = 64 n + lane
-// -> row q / 72, position q % 72, source chunk (q % 72) ^ swz(row).  Readers: K fragments (ds_read_b128, lane groups
-// {0-3,12-15,20-27},...: 16 rows with chunk g or g ^ 1) and V^T fragments (ds_read_b64_tr_b16, 32 lanes = 8 rows x 32 B)
-// both land on 16 distinct 16-byte slots of the 256-byte bank row (checked exhaustively for every wave / k step;
-// the padded 1184-byte rows of rounds 2-4 left the transpose reads 2-way conflicted).
-constexpr int kRowU = kD * 2;            // 1152
-constexpr int kTileU = kTile * kRowU;    // 73728
+// The tile image: mla_decode_tile.h.
 constexpr int kDmaPieces = kTileU / 1024 / 4;  // 18 per wave
-__device__ __forceinline__ int kv_swz(int r) { return ((r >> 3) & 1) * 5 + ((r >> 1) & 1) * 2; }
 
 // ---- Round 6: the split merge + W_UV projection + act_quant INSIDE the decode launch (FUSED = true).
 //
@@ -88,9 +72,6 @@ struct MlaFuse {
 constexpr int kFuseMaxGroups = 4096;
 constexpr uint64_t kFuseTimeoutTicks = 20000000ull;  // 200 ms of the 100 MHz wall clock
 
-__device__ __forceinline__ void store16_sc1(void* dst, i32x4 v) {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
-}
 __device__ __forceinline__ uint32_t load_sc1(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // This wave's two 16-column tiles of W_UV[h] (wave w owns output columns [32 w, 32 w + 32)) and the head's four K-block scales.
@@ -317,9 +298,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
     const uint32_t lds0 = lds_offset_of(smem);
     // rows past the sequence end re-read the tile's last valid row: finite, and their probabilities are exactly 0
     auto issue = [&](const bf16_t* src, int valid, int buf) {
-        const uint64_t a = (uint64_t)src;
-        const bf16_t* sb = (const bf16_t*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
-                                           (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a));
+        const bf16_t* sb = uniform_ptr(src);
 #pragma unroll
         for (int i = 0; i < kDmaPieces; ++i)
             glds16_sbase<true>(sb, (uint32_t)(min(prow[i], valid - 1) * kRowU) + pswz[i],
@@ -328,18 +307,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
     // FUSED: an empty split still has a head of the tail to do -- it runs the rest of the kernel over zero tiles (zero rows, LSE = -inf)
     const bool empty = FUSED && tile0 >= tile1;
     if (!FUSED && tile0 >= tile1) {  // an empty split publishes LSE = -inf and zero rows (nothing of it is read by the merge)
-        if (num_splits > 1) {
-            if (tid < 16 && h0 + tid < H) part_lse[((int64_t)b * H + h0 + tid) * num_splits + split] = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int chunk = tid + i * 256, hr = chunk >> 6, c8 = chunk & 63;
-                if (h0 + hr < H)
-                    *reinterpret_cast<i32x4*>(part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8) = i32x4{0, 0, 0, 0};
-            }
-        } else {
-            for (int i = tid; i < 16 * kC / 8; i += 256)
-                if (h0 + (i >> 6) < H) *reinterpret_cast<i32x4*>(out + ((int64_t)b * H + h0 + (i >> 6)) * kC + (i & 63) * 8) = i32x4{0, 0, 0, 0};
-        }
+        mla_publish_empty_split(part_o, part_lse, out, b, H, h0, split, num_splits, tid);
         return;
     }
     if (!empty) issue(page_src(first_pg, tile0 * kTile), min(kTile, L - tile0 * kTile), 0);
@@ -353,7 +321,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             const int c = tid + i * 256;
-            if (c < 16 * 72) *reinterpret_cast<i32x4*>(q_lds + (c / 72) * kRowU + (((c % 72) ^ kv_swz(c / 72)) << 4)) = qreg[i];
+            if (c < 16 * 72) mla_q_store(q_lds, c, qreg[i]);
         }
     }
     // page ids of the following tiles (none at one tile per split, the short-context shape: no table load, and no wait of the
@@ -374,25 +342,11 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
         m_run[r] = -INFINITY;
         l_run[r] = 0.f;
     }
-    // fragment addressing inside a tile image (see the layout note above)
-    const int ksw = kv_swz(j);                                    // row wave*16 + j: bits 1 and 3 are j's
-    const int koff0 = (wave * 16 + j) * kRowU + ((g ^ ksw) << 4);  // even k steps; odd ones: chunk ^ 4
-    const int koff1 = (wave * 16 + j) * kRowU + (((g ^ ksw) ^ 4) << 4);
-    const int vsw = (g & 1) * 5 + ((j >> 3) & 1) * 2;             // rows ks*32 + g*8 + (j>>2) (+4): bit 3 = g & 1, bit 1 = j >> 3
-    const int vrow_off = (g * 8 + (j >> 2)) * kRowU + wave * 256 + ((((j >> 1) & 1) ^ (vsw & 1)) << 4) + (j & 1) * 8;
-    int vx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) vx[k] = ((2 * k) ^ (vsw & 6)) << 4;
+    const MlaFrag frag = mla_frag(wave, j, g);
 
     __syncthreads();  // Q and the page list are visible (the first tile may still be in flight)
-    s16x8 qf[18];     // lane (j, g): elements [32 kk + 8 g, +8) of head j
-    {
-        const uint8_t* q_lds = kv_lds + kTileU;
-        const int ksw0 = kv_swz(j);
-#pragma unroll
-        for (int kk = 0; kk < 18; ++kk)
-            qf[kk] = *reinterpret_cast<const s16x8*>(q_lds + j * kRowU + (kk >> 1) * 128 + (((g + 4 * (kk & 1)) ^ ksw0) << 4));
-    }
+    s16x8 qf[18];
+    mla_q_frags(qf, kv_lds + kTileU, j, g);
     if (tile0 + 1 < tile1) {
         __syncthreads();  // every wave has its copy of Q: buffer 1 may be overwritten
         issue(tile_src(tile0 + 1), min(kTile, L - (tile0 + 1) * kTile), 1);
@@ -410,100 +364,19 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
         if (FUSED && tile + 1 == tile1 && uv_mine) mla_uv_load(uvw, fuse, h0 + split, wave, j, g);
         const uint8_t* kv = kv_lds + buf * kTileU;
         CHITU_PROBE_MARK(10);
-
-        // ---- S = Q K^T for this wave's 16 tokens (two accumulators: no 18-deep dependent chain)
-        f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 18; kk += 2) {
-            const s16x8 k0 = *reinterpret_cast<const s16x8*>(kv + koff0 + (kk >> 1) * 128);
-            const s16x8 k1 = *reinterpret_cast<const s16x8*>(kv + koff1 + (kk >> 1) * 128);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk], k0, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk + 1], k1, s1, 0, 0, 0);
-        }
-        // lane holds S[head 4g+r][token wave*16+j]
-        CHITU_PROBE_MARK(11);
-        const bool tok_ok = (wave * 16 + j) < valid;
-        float sv[4], mx[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sv[r] = tok_ok ? (s0[r] + s1[r]) * scale : -INFINITY;
-            mx[r] = row16_reduce_max(sv[r]);
-        }
-        if (j == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red_max[wave * 16 + g * 4 + r] = mx[r];
-        }
-        __syncthreads();
-        float alpha[4], psum[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int hh = g * 4 + r;
-            const float mt = __builtin_fmaxf(__builtin_fmaxf(red_max[hh], red_max[16 + hh]),
-                                             __builtin_fmaxf(red_max[32 + hh], red_max[48 + hh]));
-            const float m_new = __builtin_fmaxf(m_run[r], mt);  // finite: the tile's first token is valid
-            alpha[r] = __expf(m_run[r] - m_new);
-            m_run[r] = m_new;
-            const float p = __expf(sv[r] - m_new);
-            psum[r] = row16_reduce_sum(p);
-            p_lds[hh * kPStride + wave * 16 + j] = f32_to_bf16(p);
-        }
-        if (j == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red_sum[wave * 16 + g * 4 + r] = psum[r];
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[c][r] *= alpha[r];
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int hh = g * 4 + r;
-            l_run[r] = l_run[r] * alpha[r] + (red_sum[hh] + red_sum[16 + hh] + red_sum[32 + hh] + red_sum[48 + hh]);
-        }
-
-        // ---- O += P V : this wave owns latent columns [wave*128, wave*128+128)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const s16x8 pfrag = *reinterpret_cast<const s16x8*>(p_lds + j * kPStride + ks * 32 + g * 8);
-            const uint8_t* vbase = kv + vrow_off + ks * 32 * kRowU;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint8_t* va = vbase + vx[c & 3] + (c >> 2) * 128;
-                const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va));
-                const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va + 4 * kRowU));
-                s16x8 vf;
-                vf[0] = v0[0]; vf[1] = v0[1]; vf[2] = v0[2]; vf[3] = v0[3];
-                vf[4] = v1[0]; vf[5] = v1[1]; vf[6] = v1[2]; vf[7] = v1[3];
-                o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, vf, o[c], 0, 0, 0);
-            }
-        }
+        mla_tile_step(kv, qf, frag, valid, scale, p_lds, red_max, red_sum, o, m_run, l_run, wave, j, g);
     }
 
-    // ---- epilogue: lane holds O[head 4g+r][col wave*128 + c*16 + j]
     CHITU_PROBE_MARK(12);
+    float inv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) inv[r] = empty ? 0.f : 1.0f / l_run[r];
     if (num_splits == 1) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int h = h0 + g * 4 + r;
-            if (h >= H) continue;
-            const float inv = empty ? 0.f : 1.0f / l_run[r];
-            bf16_t* dst = out + ((int64_t)b * H + h) * kC + wave * 128 + j;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) dst[c * 16] = f32_to_bf16(o[c][r] * inv);
-        }
+        mla_store_out_rows(out, o, inv, b, H, h0, wave, j, g);
         return;
     }
-    // split partials: transposed through LDS (the KV tiles are dead) so every thread stores 16-B pieces of whole rows; they
-    // leave as BF16 (the normalised o of a split is an attention output: the merge's convex combination keeps the 2^-9
-    // rounding below the final output's own) + the fp32 LSE
-    __syncthreads();
-    bf16_t* o_lds = reinterpret_cast<bf16_t*>(kv_lds);  // [16][512] bf16 = 16 KB
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float inv = empty ? 0.f : 1.0f / l_run[r];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o_lds[(g * 4 + r) * kC + wave * 128 + c * 16 + j] = f32_to_bf16(o[c][r] * inv);
+    for (int r = 0; r < 4; ++r) {  // the fp32 LSE of the split's rows
         const int h = h0 + g * 4 + r;
         if (wave == 0 && j == 0 && h < H) {
             float* lp = part_lse + ((int64_t)b * H + h) * num_splits + split;
@@ -512,19 +385,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
             else *lp = lv;
         }
     }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int chunk = tid + i * 256;
-        const int hr = chunk >> 6, c8 = chunk & 63;
-        if (h0 + hr < H) {
-            const i32x4 v = *reinterpret_cast<const i32x4*>(o_lds + hr * kC + c8 * 8);
-            bf16_t* dst = part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8;
-            // write-through (sc1): partials left DIRTY in the L2s would be flushed by the end-of-kernel release, in
-            // front of the launch that reads them back; streamed out here they overlap the other workgroups
-            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
-        }
-    }
+    mla_store_partial_rows(part_o, reinterpret_cast<bf16_t*>(kv_lds), o, inv, b, H, h0, split, num_splits, tid, wave, j, g);
     CHITU_PROBE_MARK(13);
     if (FUSED) {
         // scratch: the second tile buffer's first bytes (the partial transpose above used the first buffer's)
@@ -571,8 +432,6 @@ __global__ __launch_bounds__(128) void mla_merge_kernel(const bf16_t* __restrict
     *reinterpret_cast<i32x2*>(out + bh * kC + threadIdx.x * 4) = o2;
 }
 
-// The merge launch for the other producer of this workspace layout (mla_decode_kv_fp8.hip: a kernel is launched from the
-// translation unit that defines it).
 void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, int64_t rows, int num_splits, hipStream_t st) {
     hipLaunchKernelGGL(mla_merge_kernel, dim3((unsigned)rows), dim3(128), 0, st, part_o, part_lse, out, num_splits);
 }
@@ -604,34 +463,22 @@ extern "C" int chitu_hip_mla_decode(const void* q_nope, int64_t qn_stride_b, int
                                     int32_t rope_dim, int32_t num_splits, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
     using namespace chitu;
-    CHITU_REQUIRE(q_nope && q_pe && kv_cache && block_table && seqlens);
     CHITU_REQUIRE(out_bf16 || num_splits > 1);  // no out: leave the split partials for a fused consumer
-    CHITU_REQUIRE(batch >= 0 && heads >= 1 && num_pages >= 1 && table_stride >= 1);
-    CHITU_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)q_nope & 15) == 0 && ((uintptr_t)q_pe & 15) == 0);  // 16-byte loads
-    if (kv_lora_rank != kC || rope_dim != kR) return CHITU_ERR_UNSUPPORTED;
-    if (page_size < kTile || page_size % kTile != 0) return CHITU_ERR_UNSUPPORTED;
-    CHITU_REQUIRE(num_splits >= 1 && num_splits <= 256);
-    // the kernel's split arithmetic is 32-bit: tiles the table can address x (splits + 1) must stay below 2^31
-    CHITU_REQUIRE((int64_t)table_stride * (page_size / kTile) * (num_splits + 1) < (1ll << 31));
+    if (int rc = mla_decode_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, heads, num_pages, page_size, table_stride,
+                                       kv_lora_rank, rope_dim, num_splits, 1))
+        return rc;
     if (batch == 0) return CHITU_OK;
     bf16_t* part_o = nullptr;
     float* part_lse = nullptr;
-    if (num_splits > 1) {
-        // workspace: bf16 partial rows [batch, heads, splits, 512] | fp32 LSE [batch, heads, splits]
-        const int64_t need = (int64_t)batch * heads * num_splits * (kC * 2 + 4);
-        CHITU_REQUIRE(workspace && workspace_bytes >= need);
-        part_o = (bf16_t*)workspace;
-        part_lse = (float*)(part_o + (int64_t)batch * heads * num_splits * kC);
-    }
+    if (num_splits > 1)
+        if (int rc = mla_decode_carve_workspace(workspace, workspace_bytes, batch, heads, num_splits, &part_o, &part_lse)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((unsigned)num_splits, (unsigned)batch, (unsigned)((heads + 15) / 16));
     hipLaunchKernelGGL(mla_decode_kernel<false>, grid, dim3(256), mla_decode_lds_bytes<false>(), st, (const bf16_t*)q_nope, qn_stride_b,
                        qn_stride_h, (const bf16_t*)q_pe, qp_stride_b, qp_stride_h, (const bf16_t*)kv_cache,
                        num_pages, (int)page_size, block_table, (int)table_stride, seqlens, softmax_scale,
                        part_o, part_lse, (bf16_t*)out_bf16, (int)heads, (int)num_splits, MlaFuse{});
-    if (num_splits > 1 && out_bf16)
-        hipLaunchKernelGGL(mla_merge_kernel, dim3((unsigned)(batch * heads)), dim3(128), 0, st, part_o,
-                           part_lse, (bf16_t*)out_bf16, (int)num_splits);
+    if (num_splits > 1 && out_bf16) launch_mla_merge(part_o, part_lse, (bf16_t*)out_bf16, (int64_t)batch * heads, (int)num_splits, st);
     CHITU_RETURN_LAUNCH_STATUS();
 }
 
@@ -649,21 +496,18 @@ extern "C" int chitu_hip_mla_decode_merge_uv_quant_fp8(
     int64_t scale_offset, int64_t scale_stride_h, int64_t scale_stride_k, void* q_fp8, float* q_scales, int32_t tile_major,
     uint32_t* tickets, void* stream) {
     using namespace chitu;
-    CHITU_REQUIRE(q_nope && q_pe && kv_cache && block_table && seqlens && w_fp8 && scale && q_fp8 && q_scales && tickets);
-    CHITU_REQUIRE(batch >= 0 && heads >= 1 && num_pages >= 1 && table_stride >= 1 && w_stride_h % 16 == 0);
-    CHITU_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)q_nope & 15) == 0 && ((uintptr_t)q_pe & 15) == 0);  // 16-byte loads
+    CHITU_REQUIRE(w_fp8 && scale && q_fp8 && q_scales && tickets && w_stride_h % 16 == 0);
     CHITU_REQUIRE(((uintptr_t)w_fp8 & 15) == 0 && ((uintptr_t)tickets & 3) == 0);
-    if (kv_lora_rank != kC || rope_dim != kR) return CHITU_ERR_UNSUPPORTED;
-    if (page_size < kTile || page_size % kTile != 0) return CHITU_ERR_UNSUPPORTED;
-    CHITU_REQUIRE(num_splits >= 2 && num_splits <= 256);  // one split: chitu_hip_mla_decode + chitu_hip_absorb_uv_quant_fp8
-    CHITU_REQUIRE((int64_t)table_stride * (page_size / kTile) * (num_splits + 1) < (1ll << 31));
+    // at least two splits: one split is chitu_hip_mla_decode + chitu_hip_absorb_uv_quant_fp8
+    if (int rc = mla_decode_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, heads, num_pages, page_size, table_stride,
+                                       kv_lora_rank, rope_dim, num_splits, 2))
+        return rc;
     const int hb = (heads + 15) / 16;
     if ((int64_t)batch * hb > kFuseMaxGroups) return CHITU_ERR_UNSUPPORTED;
     if (batch == 0) return CHITU_OK;
-    const int64_t need = (int64_t)batch * heads * num_splits * (kC * 2 + 4);
-    CHITU_REQUIRE(workspace && workspace_bytes >= need);
-    bf16_t* part_o = (bf16_t*)workspace;
-    float* part_lse = (float*)(part_o + (int64_t)batch * heads * num_splits * kC);
+    bf16_t* part_o;
+    float* part_lse;
+    if (int rc = mla_decode_carve_workspace(workspace, workspace_bytes, batch, heads, num_splits, &part_o, &part_lse)) return rc;
     const MlaFuse fuse{(const fp8_t*)w_fp8, w_stride_h, scale, scale_offset, scale_stride_h, scale_stride_k, (fp8_t*)q_fp8, q_scales,
                        (int)tile_major, tickets};
     const dim3 grid((unsigned)num_splits, (unsigned)batch, (unsigned)hb);

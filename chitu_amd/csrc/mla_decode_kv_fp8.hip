@@ -1,13 +1,13 @@
 // MLA (absorb mode) paged decode attention over the FP8 latent KV cache (new: no reference counterpart).
 //
-// chitu_hip_mla_decode's contract, grid, split logic and arithmetic (mla_decode.hip) with the cache holding 656-byte rows
+// chitu_hip_mla_decode's contract, grid and split logic (mla_decode.hip) with the cache holding 656-byte rows
 // (mla_kv_fp8.hip: 512 e4m3 codes | four power-of-two fp32 scales | 64 bf16 rope values): 0.569 of the bytes a bf16 row streams.
 // q stays bf16.  The latent is widened to bf16 as code * 2^e, which is exact, so the tile the MFMAs read holds the very bits
-// chitu_hip_mla_kv_dequant_fp8 would have written to a bf16 cache; QK^T, the online softmax, P -> bf16 and PV then run in
-// mla_decode_kernel's order and the output is bit-identical to chitu_hip_mla_decode on the dequantised cache at the same
-// num_splits (tests/test_gpu_mla_kv_fp8.py).
+// chitu_hip_mla_kv_dequant_fp8 would have written to a bf16 cache; the tile step and the epilogue behind it are the ones
+// mla_decode_kernel runs (mla_decode_tile.h), so the output is bit-identical to chitu_hip_mla_decode on the dequantised cache at
+// the same num_splits (tests/test_gpu_mla_kv_fp8.py).
 //
-// How bytes move.  LDS holds ONE bf16 tile image (mla_decode.hip's: [64][1152 B], chunk c of row r at c ^ kv_swz(r)) and TWO
+// How bytes move.  LDS holds ONE bf16 tile image (mla_decode_tile.h: [64][1152 B], chunk c of row r at c ^ kv_swz(r)) and TWO
 // fp8 staging buffers [64][656 B] = 41 KiB each: 73.7 + 2 x 42.0 KB + P, the softmax exchange and the page ids = 158.75 KB of
 // the CU's 160.  (Two images do not fit beside a staging buffer.)  Per tile:
 //   wait for the tile's DMA | barrier | request the NEXT tile into the other staging buffer | widen staging -> image | barrier
@@ -27,24 +27,16 @@
 // coverage of the image, in tests/test_mla_kv_fp8_host.py.
 #include "common.h"
 #include "lds_dma.h"
+#include "mla_decode_tile.h"
 #include "mla_kv_fp8.h"
 
 namespace chitu {
 
-void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, int64_t rows, int num_splits, hipStream_t st);  // mla_decode.hip
-
-namespace kvfp8 {
-
-constexpr int kC = 512, kR = 64, kD = kC + kR, kTile = 64, kPStride = 72, kMaxTilesLds = 512;
-constexpr int kRowU = kD * 2;                    // 1152: a row of the bf16 image
-constexpr int kTileU = kTile * kRowU;            // 73728
 constexpr int kRowChunks = kKvFp8Row / 16;       // 41
 constexpr int kStageU = kTile * kKvFp8Row;       // 41984 = 41 pieces of 1 KiB
 constexpr int kStagePieces = kStageU / 1024;     // 41: wave w requests pieces w, w + 4, ...
 constexpr int kStageChunks = kStageU / 16;       // 2624
 constexpr int kStages = 2;                       // staging buffers: tile t + 1 lands while tile t is widened and multiplied
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-__device__ __forceinline__ int kv_swz(int r) { return ((r >> 3) & 1) * 5 + ((r >> 1) & 1) * 2; }
 
 // grid (num_splits, batch, heads/16); block 256
 __global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
@@ -71,19 +63,8 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
     const int n_tiles = (L + kTile - 1) / kTile;
     const int tile0 = (int)((unsigned)n_tiles * (unsigned)split / (unsigned)num_splits);
     const int tile1 = (int)((unsigned)n_tiles * (unsigned)(split + 1) / (unsigned)num_splits);
-    if (tile0 >= tile1) {  // an empty split publishes LSE = -inf and zero rows (nothing of it is read by the merge)
-        if (num_splits > 1) {
-            if (tid < 16 && h0 + tid < H) part_lse[((int64_t)b * H + h0 + tid) * num_splits + split] = -INFINITY;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int chunk = tid + i * 256, hr = chunk >> 6, c8 = chunk & 63;
-                if (h0 + hr < H)
-                    *reinterpret_cast<i32x4*>(part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8) = i32x4{0, 0, 0, 0};
-            }
-        } else {
-            for (int i = tid; i < 16 * kC / 8; i += 256)
-                if (h0 + (i >> 6) < H) *reinterpret_cast<i32x4*>(out + ((int64_t)b * H + h0 + (i >> 6)) * kC + (i & 63) * 8) = i32x4{0, 0, 0, 0};
-        }
+    if (tile0 >= tile1) {
+        mla_publish_empty_split(part_o, part_lse, out, b, H, h0, split, num_splits, tid);
         return;
     }
     const bool pages_in_lds = (tile1 - tile0) <= kMaxTilesLds;
@@ -114,8 +95,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
                 glds16_sbase<true>(sb, (uint32_t)(min(prow[i], valid - 1) * kKvFp8Row) + poff[i], lds_stage + (uint32_t)(buf * kStageU + (wave + 4 * i) * 1024));
     };
     issue(tile_src(tile0), min(kTile, L - tile0 * kTile), 0);
-    {   // Q (16 heads x 576): 1152 chunks of 16 B, <= 5 per thread, coalesced, into the image's own layout (row = head, chunk c
-        // at c ^ swz(row)); every wave then reads all of it back like a K fragment: the A operand lives in registers
+    {   // Q (16 heads x 576): 1152 chunks of 16 B, <= 5 per thread, coalesced, into the image; every wave then reads all of it back
 #pragma unroll
         for (int i = 0; i < 5; ++i) {
             const int c = tid + i * 256;
@@ -123,7 +103,7 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
                 const int row = c / 72, col = c % 72;
                 const int h = min(h0 + row, H - 1);
                 const bf16_t* src = col < 64 ? q_nope + b * qn_sb + h * qn_sh + col * 8 : q_pe + b * qp_sb + h * qp_sh + (col - 64) * 8;
-                *reinterpret_cast<i32x4*>(kv_lds + row * kRowU + ((col ^ kv_swz(row)) << 4)) = *reinterpret_cast<const i32x4*>(src);
+                mla_q_store(kv_lds, c, *reinterpret_cast<const i32x4*>(src));
             }
         }
     }
@@ -143,23 +123,13 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
         m_run[r] = -INFINITY;
         l_run[r] = 0.f;
     }
-    // fragment addressing inside the image (mla_decode.hip's)
-    const int ksw = kv_swz(j);
-    const int koff0 = (wave * 16 + j) * kRowU + ((g ^ ksw) << 4);
-    const int koff1 = (wave * 16 + j) * kRowU + (((g ^ ksw) ^ 4) << 4);
-    const int vsw = (g & 1) * 5 + ((j >> 3) & 1) * 2;
-    const int vrow_off = (g * 8 + (j >> 2)) * kRowU + wave * 256 + ((((j >> 1) & 1) ^ (vsw & 1)) << 4) + (j & 1) * 8;
-    int vx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) vx[k] = ((2 * k) ^ (vsw & 6)) << 4;
+    const MlaFrag frag = mla_frag(wave, j, g);
     // the widening pass: which of its two image chunks a lane stores first (see the layout note above)
     const int odd_first = (lane >> 4) & 1;
 
     __syncthreads();  // Q and the page list are visible
-    s16x8 qf[18];     // lane (j, g): elements [32 kk + 8 g, +8) of head j
-#pragma unroll
-    for (int kk = 0; kk < 18; ++kk)
-        qf[kk] = *reinterpret_cast<const s16x8*>(kv_lds + j * kRowU + (kk >> 1) * 128 + (((g + 4 * (kk & 1)) ^ ksw) << 4));
+    s16x8 qf[18];
+    mla_q_frags(qf, kv_lds, j, g);
 
     for (int tile = tile0; tile < tile1; ++tile) {
         const int valid = min(kTile, L - tile * kTile);
@@ -190,116 +160,24 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kv_fp8_kernel(
                 *reinterpret_cast<const i32x4*>(stage + row * kKvFp8Row + kKvFp8RopeOff + pos * 16);
         }
         __syncthreads();   // the image is complete
-        const uint8_t* kv = kv_lds;
-
-        // ---- S = Q K^T for this wave's 16 tokens (two accumulators: no 18-deep dependent chain)
-        f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int kk = 0; kk < 18; kk += 2) {
-            const s16x8 k0 = *reinterpret_cast<const s16x8*>(kv + koff0 + (kk >> 1) * 128);
-            const s16x8 k1 = *reinterpret_cast<const s16x8*>(kv + koff1 + (kk >> 1) * 128);
-            s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk], k0, s0, 0, 0, 0);
-            s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk + 1], k1, s1, 0, 0, 0);
-        }
-        // lane holds S[head 4g+r][token wave*16+j]
-        const bool tok_ok = (wave * 16 + j) < valid;
-        float sv[4], mx[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            sv[r] = tok_ok ? (s0[r] + s1[r]) * scale : -INFINITY;
-            mx[r] = row16_reduce_max(sv[r]);
-        }
-        if (j == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red_max[wave * 16 + g * 4 + r] = mx[r];
-        }
-        __syncthreads();
-        float alpha[4], psum[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int hh = g * 4 + r;
-            const float mt = __builtin_fmaxf(__builtin_fmaxf(red_max[hh], red_max[16 + hh]),
-                                             __builtin_fmaxf(red_max[32 + hh], red_max[48 + hh]));
-            const float m_new = __builtin_fmaxf(m_run[r], mt);  // finite: the tile's first token is valid
-            alpha[r] = __expf(m_run[r] - m_new);
-            m_run[r] = m_new;
-            const float p = __expf(sv[r] - m_new);
-            psum[r] = row16_reduce_sum(p);
-            p_lds[hh * kPStride + wave * 16 + j] = f32_to_bf16(p);
-        }
-        if (j == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red_sum[wave * 16 + g * 4 + r] = psum[r];
-        }
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) o[c][r] *= alpha[r];
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int hh = g * 4 + r;
-            l_run[r] = l_run[r] * alpha[r] + (red_sum[hh] + red_sum[16 + hh] + red_sum[32 + hh] + red_sum[48 + hh]);
-        }
-
-        // ---- O += P V : this wave owns latent columns [wave*128, wave*128+128)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const s16x8 pfrag = *reinterpret_cast<const s16x8*>(p_lds + j * kPStride + ks * 32 + g * 8);
-            const uint8_t* vbase = kv + vrow_off + ks * 32 * kRowU;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                const uint8_t* va = vbase + vx[c & 3] + (c >> 2) * 128;
-                const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va));
-                const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va + 4 * kRowU));
-                s16x8 vf;
-                vf[0] = v0[0]; vf[1] = v0[1]; vf[2] = v0[2]; vf[3] = v0[3];
-                vf[4] = v1[0]; vf[5] = v1[1]; vf[6] = v1[2]; vf[7] = v1[3];
-                o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, vf, o[c], 0, 0, 0);
-            }
-        }
+        mla_tile_step(kv_lds, qf, frag, valid, scale, p_lds, red_max, red_sum, o, m_run, l_run, wave, j, g);
     }
 
-    // ---- epilogue: lane holds O[head 4g+r][col wave*128 + c*16 + j]
+    float inv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) inv[r] = 1.0f / l_run[r];
     if (num_splits == 1) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int h = h0 + g * 4 + r;
-            if (h >= H) continue;
-            const float inv = 1.0f / l_run[r];
-            bf16_t* dst = out + ((int64_t)b * H + h) * kC + wave * 128 + j;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) dst[c * 16] = f32_to_bf16(o[c][r] * inv);
-        }
+        mla_store_out_rows(out, o, inv, b, H, h0, wave, j, g);
         return;
     }
-    // split partials: transposed through LDS (the image is dead) so every thread stores 16-B pieces of whole rows: bf16
-    // normalised rows + the fp32 LSE, the workspace layout mla_merge_kernel and mla_merge_uv_quant_kernel read
-    __syncthreads();
-    bf16_t* o_lds = reinterpret_cast<bf16_t*>(kv_lds);  // [16][512] bf16 = 16 KB
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float inv = 1.0f / l_run[r];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) o_lds[(g * 4 + r) * kC + wave * 128 + c * 16 + j] = f32_to_bf16(o[c][r] * inv);
+    for (int r = 0; r < 4; ++r) {  // the fp32 LSE of the split's rows
         const int h = h0 + g * 4 + r;
         if (wave == 0 && j == 0 && h < H) part_lse[((int64_t)b * H + h) * num_splits + split] = m_run[r] + __logf(l_run[r]);
     }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int chunk = tid + i * 256;
-        const int hr = chunk >> 6, c8 = chunk & 63;
-        if (h0 + hr < H) {
-            const i32x4 v = *reinterpret_cast<const i32x4*>(o_lds + hr * kC + c8 * 8);
-            bf16_t* dst = part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8;
-            // write-through (sc1), as in mla_decode.hip: the partials stream out instead of waiting dirty for the end-of-kernel release
-            asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
-        }
-    }
+    mla_store_partial_rows(part_o, reinterpret_cast<bf16_t*>(kv_lds), o, inv, b, H, h0, split, num_splits, tid, wave, j, g);
 }
 
-}  // namespace kvfp8
 }  // namespace chitu
 
 extern "C" int chitu_hip_mla_decode_kv_fp8(const void* q_nope, int64_t qn_stride_b, int64_t qn_stride_h,
@@ -311,26 +189,15 @@ extern "C" int chitu_hip_mla_decode_kv_fp8(const void* q_nope, int64_t qn_stride
                                            int32_t rope_dim, int32_t num_splits, void* workspace,
                                            int64_t workspace_bytes, void* stream) {
     using namespace chitu;
-    using namespace chitu::kvfp8;
-    CHITU_REQUIRE(q_nope && q_pe && kv_cache && block_table && seqlens);
     CHITU_REQUIRE(out_bf16 || num_splits > 1);  // no out: leave the split partials for a fused consumer
-    CHITU_REQUIRE(batch >= 0 && heads >= 1 && num_pages >= 1 && table_stride >= 1);
-    CHITU_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)q_nope & 15) == 0 && ((uintptr_t)q_pe & 15) == 0);  // 16-byte loads
-    if (kv_lora_rank != kC || rope_dim != kR) return CHITU_ERR_UNSUPPORTED;
-    if (page_size < kTile || page_size % kTile != 0) return CHITU_ERR_UNSUPPORTED;
-    CHITU_REQUIRE(num_splits >= 1 && num_splits <= 256);
-    // the kernel's split arithmetic is 32-bit: tiles the table can address x (splits + 1) must stay below 2^31
-    CHITU_REQUIRE((int64_t)table_stride * (page_size / kTile) * (num_splits + 1) < (1ll << 31));
+    if (int rc = mla_decode_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, heads, num_pages, page_size, table_stride,
+                                       kv_lora_rank, rope_dim, num_splits, 1))
+        return rc;
     if (batch == 0) return CHITU_OK;
     bf16_t* part_o = nullptr;
     float* part_lse = nullptr;
-    if (num_splits > 1) {
-        // workspace: bf16 partial rows [batch, heads, splits, 512] | fp32 LSE [batch, heads, splits]
-        const int64_t need = (int64_t)batch * heads * num_splits * (kC * 2 + 4);
-        CHITU_REQUIRE(workspace && workspace_bytes >= need);
-        part_o = (bf16_t*)workspace;
-        part_lse = (float*)(part_o + (int64_t)batch * heads * num_splits * kC);
-    }
+    if (num_splits > 1)
+        if (int rc = mla_decode_carve_workspace(workspace, workspace_bytes, batch, heads, num_splits, &part_o, &part_lse)) return rc;
     hipStream_t st = (hipStream_t)stream;
     // the opt-in above 64 KB of dynamic LDS is set on every call (per device and cheap, as in mla_decode.hip)
     const size_t lds = kTileU + kStages * kStageU + 16 * kPStride * 2 + 2 * 64 * sizeof(float) + kMaxTilesLds * sizeof(int);

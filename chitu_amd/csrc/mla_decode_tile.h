@@ -1,0 +1,219 @@
+// What the MLA paged decode kernels share (mla_decode.hip: bf16 cache, mla_decode_kv_fp8.hip: fp8 latent cache): the bf16 tile
+// image and its fragment addressing, the tile step (QK^T, online softmax, P -> bf16, PV), the empty-split publication, the
+// epilogue and the host-side argument checks.  The two kernels differ in how a tile's bytes reach the image, and in nothing
+// behind that: the fp8 kernel's output is bit-identical to the bf16 kernel's on the dequantised cache because both run this text.
+#pragma once
+#include "common.h"
+
+namespace chitu {
+
+constexpr int kC = 512;        // kv_lora_rank (latent / V width)
+constexpr int kR = 64;         // qk_rope_head_dim
+constexpr int kD = kC + kR;    // cached row width (576)
+constexpr int kTile = 64;      // KV tokens per tile
+constexpr int kPStride = 72;   // P row stride in bf16 elements (64 + 8 pad)
+constexpr int kMaxTilesLds = 512;  // page ids cached in LDS per split (32k tokens)
+
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+
+// LDS image of a tile: [64 rows][1152 B] unpadded, the 16-byte chunk c of row r stored at c ^ swz(r),
+// swz(r) = 5 * bit3(r) + 2 * bit1(r).  A DMA piece is 1 KiB of the image, lane-linear (lds_dma.h): image chunk q = 64 n + lane
+// -> row q / 72, position q % 72, source chunk (q % 72) ^ swz(row).  Readers: K fragments (ds_read_b128, lane groups
+// {0-3,12-15,20-27},...: 16 rows with chunk g or g ^ 1) and V^T fragments (ds_read_b64_tr_b16, 32 lanes = 8 rows x 32 B)
+// both land on 16 distinct 16-byte slots of the 256-byte bank row (checked exhaustively for every wave / k step;
+// the padded 1184-byte rows of rounds 2-4 left the transpose reads 2-way conflicted).
+constexpr int kRowU = kD * 2;            // 1152
+constexpr int kTileU = kTile * kRowU;    // 73728
+__device__ __forceinline__ int kv_swz(int r) { return ((r >> 3) & 1) * 5 + ((r >> 1) & 1) * 2; }
+
+__device__ __forceinline__ void store16_sc1(void* dst, i32x4 v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
+}
+
+// fragment addressing inside a tile image (see the layout note above) of lane (j = lane & 15, g = lane >> 4) of a wave
+struct MlaFrag {
+    int ksw, koff0, koff1, vrow_off, vx[4];
+};
+__device__ __forceinline__ MlaFrag mla_frag(int wave, int j, int g) {
+    MlaFrag f;
+    f.ksw = kv_swz(j);                                             // row wave*16 + j: bits 1 and 3 are j's
+    f.koff0 = (wave * 16 + j) * kRowU + ((g ^ f.ksw) << 4);        // even k steps; odd ones: chunk ^ 4
+    f.koff1 = (wave * 16 + j) * kRowU + (((g ^ f.ksw) ^ 4) << 4);
+    const int vsw = (g & 1) * 5 + ((j >> 3) & 1) * 2;              // rows ks*32 + g*8 + (j>>2) (+4): bit 3 = g & 1, bit 1 = j >> 3
+    f.vrow_off = (g * 8 + (j >> 2)) * kRowU + wave * 256 + ((((j >> 1) & 1) ^ (vsw & 1)) << 4) + (j & 1) * 8;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) f.vx[k] = ((2 * k) ^ (vsw & 6)) << 4;
+    return f;
+}
+
+// Q (16 heads x 576 = 1152 chunks of 16 B) in the tile image's own layout (row = head, chunk c at c ^ swz(row)): chunk c < 1152
+__device__ __forceinline__ void mla_q_store(uint8_t* img, int c, i32x4 v) {
+    *reinterpret_cast<i32x4*>(img + (c / 72) * kRowU + (((c % 72) ^ kv_swz(c / 72)) << 4)) = v;
+}
+// ... read back like a K fragment, into the registers of every wave (the A operand never changes).
+// lane (j, g): qf[kk] = elements [32 kk + 8 g, +8) of head j
+__device__ __forceinline__ void mla_q_frags(s16x8 (&qf)[18], const uint8_t* img, int j, int g) {
+    const int ksw0 = kv_swz(j);
+#pragma unroll
+    for (int kk = 0; kk < 18; ++kk)
+        qf[kk] = *reinterpret_cast<const s16x8*>(img + j * kRowU + (kk >> 1) * 128 + (((g + 4 * (kk & 1)) ^ ksw0) << 4));
+}
+
+// One 64-token tile whose image is complete at `kv` and visible to the workgroup: the caller has waited, met and issued what
+// it issues.  p_lds [16][kPStride], red_max / red_sum [4][16]: free on entry, in use until the caller's next barrier.
+__device__ __forceinline__ void mla_tile_step(const uint8_t* kv, const s16x8 (&qf)[18], const MlaFrag& f, int valid, float scale,
+                                              bf16_t* p_lds, float* red_max, float* red_sum, f32x4 (&o)[8], float (&m_run)[4],
+                                              float (&l_run)[4], int wave, int j, int g) {
+    // ---- S = Q K^T for this wave's 16 tokens (two accumulators: no 18-deep dependent chain)
+    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < 18; kk += 2) {
+        const s16x8 k0 = *reinterpret_cast<const s16x8*>(kv + f.koff0 + (kk >> 1) * 128);
+        const s16x8 k1 = *reinterpret_cast<const s16x8*>(kv + f.koff1 + (kk >> 1) * 128);
+        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk], k0, s0, 0, 0, 0);
+        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(qf[kk + 1], k1, s1, 0, 0, 0);
+    }
+    // lane holds S[head 4g+r][token wave*16+j]
+    CHITU_PROBE_MARK(11);
+    const bool tok_ok = (wave * 16 + j) < valid;
+    float sv[4], mx[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        sv[r] = tok_ok ? (s0[r] + s1[r]) * scale : -INFINITY;
+        mx[r] = row16_reduce_max(sv[r]);
+    }
+    if (j == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red_max[wave * 16 + g * 4 + r] = mx[r];
+    }
+    __syncthreads();
+    float alpha[4], psum[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int hh = g * 4 + r;
+        const float mt = __builtin_fmaxf(__builtin_fmaxf(red_max[hh], red_max[16 + hh]),
+                                         __builtin_fmaxf(red_max[32 + hh], red_max[48 + hh]));
+        const float m_new = __builtin_fmaxf(m_run[r], mt);  // finite: the tile's first token is valid
+        alpha[r] = __expf(m_run[r] - m_new);
+        m_run[r] = m_new;
+        const float p = __expf(sv[r] - m_new);
+        psum[r] = row16_reduce_sum(p);
+        p_lds[hh * kPStride + wave * 16 + j] = f32_to_bf16(p);
+    }
+    if (j == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red_sum[wave * 16 + g * 4 + r] = psum[r];
+    }
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[c][r] *= alpha[r];
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int hh = g * 4 + r;
+        l_run[r] = l_run[r] * alpha[r] + (red_sum[hh] + red_sum[16 + hh] + red_sum[32 + hh] + red_sum[48 + hh]);
+    }
+
+    // ---- O += P V : this wave owns latent columns [wave*128, wave*128+128)
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+        const s16x8 pfrag = *reinterpret_cast<const s16x8*>(p_lds + j * kPStride + ks * 32 + g * 8);
+        const uint8_t* vbase = kv + f.vrow_off + ks * 32 * kRowU;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const uint8_t* va = vbase + f.vx[c & 3] + (c >> 2) * 128;
+            const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va));
+            const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(va + 4 * kRowU));
+            s16x8 vf;
+            vf[0] = v0[0]; vf[1] = v0[1]; vf[2] = v0[2]; vf[3] = v0[3];
+            vf[4] = v1[0]; vf[5] = v1[1]; vf[6] = v1[2]; vf[7] = v1[3];
+            o[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pfrag, vf, o[c], 0, 0, 0);
+        }
+    }
+}
+
+// an empty split publishes LSE = -inf and zero rows (nothing of it is read by the merge); one split: the output rows are zero
+__device__ __forceinline__ void mla_publish_empty_split(bf16_t* part_o, float* part_lse, bf16_t* out, int b, int H, int h0, int split,
+                                                        int num_splits, int tid) {
+    if (num_splits > 1) {
+        if (tid < 16 && h0 + tid < H) part_lse[((int64_t)b * H + h0 + tid) * num_splits + split] = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int chunk = tid + i * 256, hr = chunk >> 6, c8 = chunk & 63;
+            if (h0 + hr < H)
+                *reinterpret_cast<i32x4*>(part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8) = i32x4{0, 0, 0, 0};
+        }
+    } else {
+        for (int i = tid; i < 16 * kC / 8; i += 256)
+            if (h0 + (i >> 6) < H) *reinterpret_cast<i32x4*>(out + ((int64_t)b * H + h0 + (i >> 6)) * kC + (i & 63) * 8) = i32x4{0, 0, 0, 0};
+    }
+}
+
+// ---- epilogue: lane holds O[head 4g+r][col wave*128 + c*16 + j]; inv[r]: what row r is normalised by.  One split: the rows of out
+__device__ __forceinline__ void mla_store_out_rows(bf16_t* out, const f32x4 (&o)[8], const float (&inv)[4], int b, int H, int h0,
+                                                   int wave, int j, int g) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int h = h0 + g * 4 + r;
+        if (h >= H) continue;
+        bf16_t* dst = out + ((int64_t)b * H + h) * kC + wave * 128 + j;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) dst[c * 16] = f32_to_bf16(o[c][r] * inv[r]);
+    }
+}
+// split partials: transposed through o_lds ([16][512] bf16 = 16 KB of the dead tile image) so every thread stores 16-B pieces
+// of whole rows; they leave as BF16 (the normalised o of a split is an attention output: the merge's convex combination keeps
+// the 2^-9 rounding below the final output's own) in the workspace layout mla_merge_kernel and mla_merge_uv_quant_kernel read
+__device__ __forceinline__ void mla_store_partial_rows(bf16_t* part_o, bf16_t* o_lds, const f32x4 (&o)[8], const float (&inv)[4], int b,
+                                                       int H, int h0, int split, int num_splits, int tid, int wave, int j, int g) {
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) o_lds[(g * 4 + r) * kC + wave * 128 + c * 16 + j] = f32_to_bf16(o[c][r] * inv[r]);
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int chunk = tid + i * 256;
+        const int hr = chunk >> 6, c8 = chunk & 63;
+        if (h0 + hr < H) {
+            const i32x4 v = *reinterpret_cast<const i32x4*>(o_lds + hr * kC + c8 * 8);
+            // write-through (sc1): partials left DIRTY in the L2s would be flushed by the end-of-kernel release, in
+            // front of the launch that reads them back; streamed out here they overlap the other workgroups
+            store16_sc1(part_o + (((int64_t)b * H + h0 + hr) * num_splits + split) * kC + c8 * 8, v);
+        }
+    }
+}
+
+// ---- host side of the three decode entries
+// Stage 2 (mla_decode.hip: a kernel is launched from the translation unit that defines it)
+void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, int64_t rows, int num_splits, hipStream_t st);
+
+// The argument checks the entries share, in the order their return codes depend on; min_splits: 1, or 2 where one split is
+// another entry's business.  An entry's own BAD_ARG checks come before this call, what it refuses as UNSUPPORTED behind it.
+static inline int mla_decode_check_args(const void* q_nope, const void* q_pe, const void* kv_cache, const int32_t* block_table,
+                                        const int32_t* seqlens, int32_t batch, int32_t heads, int64_t num_pages, int32_t page_size,
+                                        int32_t table_stride, int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits,
+                                        int32_t min_splits) {
+    CHITU_REQUIRE(q_nope && q_pe && kv_cache && block_table && seqlens);
+    CHITU_REQUIRE(batch >= 0 && heads >= 1 && num_pages >= 1 && table_stride >= 1);
+    CHITU_REQUIRE(((uintptr_t)kv_cache & 15) == 0 && ((uintptr_t)q_nope & 15) == 0 && ((uintptr_t)q_pe & 15) == 0);  // 16-byte loads
+    if (kv_lora_rank != kC || rope_dim != kR) return CHITU_ERR_UNSUPPORTED;
+    if (page_size < kTile || page_size % kTile != 0) return CHITU_ERR_UNSUPPORTED;
+    CHITU_REQUIRE(num_splits >= min_splits && num_splits <= 256);
+    // the kernel's split arithmetic is 32-bit: tiles the table can address x (splits + 1) must stay below 2^31
+    CHITU_REQUIRE((int64_t)table_stride * (page_size / kTile) * (num_splits + 1) < (1ll << 31));
+    return CHITU_OK;
+}
+// workspace (num_splits > 1, batch > 0): bf16 partial rows [batch, heads, splits, 512] | fp32 LSE [batch, heads, splits]
+static inline int mla_decode_carve_workspace(void* workspace, int64_t workspace_bytes, int32_t batch, int32_t heads, int32_t num_splits,
+                                             bf16_t** part_o, float** part_lse) {
+    const int64_t need = (int64_t)batch * heads * num_splits * (kC * 2 + 4);
+    CHITU_REQUIRE(workspace && workspace_bytes >= need);
+    *part_o = (bf16_t*)workspace;
+    *part_lse = (float*)(*part_o + (int64_t)batch * heads * num_splits * kC);
+    return CHITU_OK;
+}
+
+}  // namespace chitu

@@ -177,18 +177,21 @@ def test_entries_check_their_arguments_on_the_host():
     i32, i64, f32 = ctypes.c_int32, ctypes.c_int64, ctypes.c_float
     BAD_ARG, UNSUPPORTED = -1, -2
 
-    def decode(cache=p, page=64, splits=1, q=p, C=512, R=64, ws=p, out=p, batch=0):
-        return lib.chitu_hip_mla_decode_kv_fp8(q, i64(576), i64(576), q, i64(64), i64(64), cache, i64(4), i32(page), p, i32(4), p,
-                                               f32(0.1), out, i32(batch), i32(16), i32(C), i32(R), i32(splits), ws, i64(0), None)
+    # the bf16 entry has the same parameter list (asserted with the header) and shares the checks: the same cases for both
+    for entry in (lib.chitu_hip_mla_decode_kv_fp8, lib.chitu_hip_mla_decode):
 
-    assert decode() == 0  # batch 0: accepted, nothing launched
-    for page in (32, 1, 96, 0):
-        assert decode(page=page) == UNSUPPORTED, page
-    assert decode(cache=odd) == BAD_ARG and decode(q=odd) == BAD_ARG and decode(cache=nul) == BAD_ARG
-    assert decode(C=256) == UNSUPPORTED and decode(R=32) == UNSUPPORTED
-    assert decode(splits=0) == BAD_ARG and decode(splits=257) == BAD_ARG
-    assert decode(out=nul) == BAD_ARG  # no output and a single split: nothing to leave behind
-    assert decode(batch=1, splits=2, ws=nul) == BAD_ARG  # split partials need the workspace
+        def decode(cache=p, page=64, splits=1, q=p, C=512, R=64, ws=p, out=p, batch=0):
+            return entry(q, i64(576), i64(576), q, i64(64), i64(64), cache, i64(4), i32(page), p, i32(4), p,
+                         f32(0.1), out, i32(batch), i32(16), i32(C), i32(R), i32(splits), ws, i64(0), None)
+
+        assert decode() == 0  # batch 0: accepted, nothing launched
+        for page in (32, 1, 96, 0):
+            assert decode(page=page) == UNSUPPORTED, page
+        assert decode(cache=odd) == BAD_ARG and decode(q=odd) == BAD_ARG and decode(cache=nul) == BAD_ARG
+        assert decode(C=256) == UNSUPPORTED and decode(R=32) == UNSUPPORTED
+        assert decode(splits=0) == BAD_ARG and decode(splits=257) == BAD_ARG
+        assert decode(out=nul) == BAD_ARG  # no output and a single split: nothing to leave behind
+        assert decode(batch=1, splits=2, ws=nul) == BAD_ARG  # split partials need the workspace
 
     def quant(src=p, ss=576, dst=p, ds=ROW + 16, rows=0):
         return lib.chitu_hip_mla_kv_quant_fp8(src, i64(ss), dst, i64(ds), i64(rows), None)
