@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, workspace
 from ._lib import check, f32, i32, i64, ptr, require_cuda, stream_ptr
-from .ops import MLA_KV_FP8_ROW, append_mla_kv_fp8, append_to_paged_kv_cache
+from .ops import GQA_KV_FP8_ROW, MLA_KV_FP8_ROW, append_gqa_kv_fp8, append_mla_kv_fp8, append_to_paged_kv_cache
 
 __all__ = ["AttnBackend", "HipAttnBackend"]
 
@@ -23,6 +23,11 @@ __all__ = ["AttnBackend", "HipAttnBackend"]
 def is_fp8_mla_cache(kv_cache) -> bool:
     """A layer of the fp8 latent KV cache (uint8 [pages, page, 656], cache_manager.mla_kv_layout("fp8"))?"""
     return kv_cache.dtype == torch.uint8 and kv_cache.shape[-1] == MLA_KV_FP8_ROW
+
+
+def is_fp8_gqa_cache(cache) -> bool:
+    """A layer of the fp8 K or V cache (uint8 [pages, page, Hkv, 144], cache_manager.gqa_kv_layout("fp8"))?"""
+    return cache.dtype == torch.uint8 and cache.dim() == 4 and cache.shape[-1] == GQA_KV_FP8_ROW
 
 
 # Upper bound of the KV splits of the GQA decode launch (graph-static: sized from the page table's width, not from the
@@ -56,6 +61,13 @@ def _num_cus():
         return torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count
     except Exception:
         return 256
+
+
+def gqa_num_splits(batch: int, kv_heads: int, max_pages: int, page_size: int) -> int:
+    """KV splits attn_with_kvcache gives the GQA decode launch when the caller names none: graph-static (the page table's
+    width, not the lengths), never more than 16-token steps, the cap above, and _GQA_WAVES_PER_CU workgroups per CU."""
+    max_steps = max(1, max_pages * page_size // 16)
+    return max(1, min(max_steps, _GQA_MAX_SPLITS, (_GQA_WAVES_PER_CU * _num_cus()) // max(1, batch * kv_heads)))
 
 
 def choose_num_splits(batch: int, head_blocks: int, max_tiles: int, target_wgs: Optional[int] = None) -> int:
@@ -429,12 +441,20 @@ class HipAttnBackend(AttnBackend):
         q [bs, 1, Hq, 128]; k_cache / v_cache [pages, page_size, Hkv, 128]; k / v [bs, 1, Hkv, 128];
         cache_seqlens [bs] int32 (excluding this token); block_table [bs, max_pages] int32.
         Returns [bs, 1, Hq, 128].  (RefAttnBackend rejects block_table, :473 -- this is the paged path.)
+
+        k_cache / v_cache uint8 [pages, page_size, Hkv, 144] (the fp8 K / V cache): k / v are quantised as they are appended
+        (ops.append_gqa_kv_fp8, one launch for both) and chitu_hip_gqa_decode_kv_fp8 reads the pages -- same arguments, same
+        workspace; the result is bit-identical to this call on ops.gqa_kv_dequant_fp8 of the caches.
         """
         assert block_table is not None, "HipAttnBackend.attn_with_kvcache is the paged path"
         assert cache_leftpad is None and window_size == (-1, -1) and softcap == 0.0
         assert q.dim() == 4 and q.shape[1] == 1, "decode: one query token per sequence"
         require_cuda(q, k_cache, v_cache, cache_seqlens, block_table)
-        assert q.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16
+        fp8_kv = is_fp8_gqa_cache(k_cache)
+        if fp8_kv:
+            assert q.dtype == torch.bfloat16 and is_fp8_gqa_cache(v_cache) and q.shape[-1] == 128
+        else:
+            assert q.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16
         assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape
         assert cache_seqlens.dtype == torch.int32 and block_table.dtype == torch.int32 and block_table.stride(1) == 1
         bs, _, Hq, D = q.shape
@@ -444,25 +464,28 @@ class HipAttnBackend(AttnBackend):
         seqlens = cache_seqlens
         if k is not None:
             assert v is not None
-            append_to_paged_kv_cache(k_cache, block_table, k.contiguous(), cache_seqlens)
-            append_to_paged_kv_cache(v_cache, block_table, v.contiguous(), cache_seqlens)
+            if fp8_kv:
+                append_gqa_kv_fp8(k_cache, v_cache, block_table, k, v, cache_seqlens)
+            else:
+                append_to_paged_kv_cache(k_cache, block_table, k.contiguous(), cache_seqlens)
+                append_to_paged_kv_cache(v_cache, block_table, v.contiguous(), cache_seqlens)
             seqlens = cache_seqlens + 1
         q3 = q.view(bs, Hq, D)
         if not (q3.stride(-1) == 1 and q3.stride(0) % 8 == 0 and q3.stride(1) % 8 == 0 and q3.data_ptr() % 16 == 0):
             q3 = q3.contiguous()
         if num_splits is None:
-            max_steps = max(1, int(block_table.shape[1]) * int(k_cache.shape[1]) // 16)
-            num_splits = max(1, min(max_steps, _GQA_MAX_SPLITS, (_GQA_WAVES_PER_CU * _num_cus()) // max(1, bs * Hkv)))
+            num_splits = gqa_num_splits(bs, Hkv, int(block_table.shape[1]), int(k_cache.shape[1]))
         out = torch.empty(bs, Hq, D, dtype=torch.bfloat16, device=q.device)
         need = bs * Hq * num_splits * (D + 1) * 4 if num_splits > 1 else 1
         ws = workspace.get(need, q.device, "gqa")
+        entry = _lib.lib().chitu_hip_gqa_decode_kv_fp8 if fp8_kv else _lib.lib().chitu_hip_gqa_decode
         check(
-            _lib.lib().chitu_hip_gqa_decode(
+            entry(
                 ptr(q3), i64(q3.stride(0)), i64(q3.stride(1)), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]),
                 i32(k_cache.shape[1]), i32(Hkv), ptr(block_table), i32(block_table.stride(0)), ptr(seqlens),
                 f32(softmax_scale), ptr(out), i32(bs), i32(Hq), i32(D), i32(num_splits), ptr(ws), i64(ws.numel()),
                 stream_ptr(),
             ),
-            "gqa_decode",
+            "gqa_decode_kv_fp8" if fp8_kv else "gqa_decode",
         )
         return out.view(bs, 1, Hq, D)

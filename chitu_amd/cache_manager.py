@@ -36,6 +36,21 @@ def mla_kv_layout(kv_cache_dtype, kv_lora_rank=512, rope=64):
     raise ValueError(f"kv_cache_dtype must be one of {MLA_KV_CACHE_DTYPES}, got {kv_cache_dtype!r}")
 
 
+GQA_KV_CACHE_DTYPES = ("bf16", "fp8")
+
+
+def gqa_kv_layout(kv_cache_dtype, n_local_kv_heads, head_dim=128):
+    """(shape_per_sample, dtype) of one cached GQA / MHA token, for PagedKVCacheManager(k_shape_per_sample=...,
+    v_shape_per_sample=..., dtype=...) -- the same for K and for V.  "bf16": [Hkv, head_dim] bf16.  "fp8": byte rows [Hkv, 144] --
+    128 e4m3 codes, one fp32 power-of-two scale per (token, head), 12 zero bytes (csrc/gqa_kv_fp8.hip): 0.5625 of bf16's."""
+    if kv_cache_dtype == "bf16":
+        return (n_local_kv_heads, head_dim), torch.bfloat16
+    if kv_cache_dtype == "fp8":
+        assert head_dim == 128, "the fp8 K / V cache rows are defined for head_dim 128"
+        return (n_local_kv_heads, 144), torch.uint8
+    raise ValueError(f"kv_cache_dtype must be one of {GQA_KV_CACHE_DTYPES}, got {kv_cache_dtype!r}")
+
+
 class PagedKVCacheManager:
     def __init__(
         self,

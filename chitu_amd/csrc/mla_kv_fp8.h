@@ -1,4 +1,6 @@
-// The fp8 latent KV cache row (mla_kv_fp8.hip states the format) as its producers and its reader share it.
+// The fp8 latent KV cache row (mla_kv_fp8.hip states the format) as its producers and its reader share it, and the two pieces of
+// arithmetic every fp8 KV cache of this library is built from (the GQA rows of gqa_kv_fp8.h included): the scale's exponent and the
+// exact widening convert.
 #pragma once
 #include "common.h"
 
@@ -18,6 +20,16 @@ __device__ __forceinline__ i32x4 kv_fp8_widen8(uint32_t w0, uint32_t w1, float s
     r[2] = __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w1, s, false));
     r[3] = __builtin_bit_cast(int, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8((int)w1, s, true));
     return r;
+}
+
+// The scale rule of every fp8 KV cache row (MLA latent groups, GQA heads): e = the smallest integer with amax <= 448 * 2^e.
+// e from amax's own bits (no division): amax = 1.m * 2^(E - 127), 448 = 1.75 * 2^8, so e = E - 135, one more when 1.m > 1.75.
+// A zero or denormal amax (E == 0) lies below 448 * 2^-64: clamped.
+__device__ __forceinline__ int kv_fp8_exponent(float amax) {
+    const uint32_t u = __float_as_uint(amax);
+    const int E = (int)(u >> 23) & 0xff;
+    if (E == 0) return -64;
+    return max(E - 135 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0), -64);
 }
 
 }  // namespace chitu

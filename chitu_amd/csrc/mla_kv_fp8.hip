@@ -15,15 +15,6 @@
 
 namespace chitu {
 
-// e from amax's own bits (no division): amax = 1.m * 2^(E - 127), 448 = 1.75 * 2^8, so e = E - 135, one more when 1.m > 1.75.
-// A zero or denormal amax (E == 0) lies below 448 * 2^-64: clamped.
-__device__ __forceinline__ int kv_fp8_exponent(float amax) {
-    const uint32_t u = __float_as_uint(amax);
-    const int E = (int)(u >> 23) & 0xff;
-    if (E == 0) return -64;
-    return max(E - 135 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0), -64);
-}
-
 // Row `src` (576 bf16, 16-byte aligned) -> 656 bytes at `dst` (16-byte aligned).  All 64 lanes of one wave.
 __device__ __forceinline__ void kv_fp8_quant_row(int lane, const bf16_t* __restrict__ src, uint8_t* __restrict__ dst) {
 #pragma clang fp contract(off)

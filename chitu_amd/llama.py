@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from . import graphs, ops
 from . import tensor_parallel as tp
 from .attn_backend import HipAttnBackend
-from .cache_manager import PagedKVCacheManager
+from .cache_manager import PagedKVCacheManager, gqa_kv_layout
 
 
 @dataclass
@@ -36,6 +36,7 @@ class LlamaArgs:
     ffn_dim: int = 14336
     norm_eps: float = 1e-5
     rope_theta: float = 500000.0
+    kv_cache_dtype: str = "bf16"  # "fp8": 144-byte K / V rows per token and head (cache_manager.gqa_kv_layout), quantised as they are appended
 
     @property
     def head_dim(self):
@@ -79,6 +80,7 @@ class LlamaAttention(torch.nn.Module):
         self.layer_id, self.cache, self.attn_backend = layer_id, cache, attn_backend
         self.hd = args.head_dim
         self.hq, self.hkv = args.n_heads // t, args.n_kv_heads // t
+        self.fp8_kv = args.kv_cache_dtype == "fp8"
         # merged [wq | wk | wv] rows (ColumnParallel: heads split across ranks), wo RowParallel
         self.wqkv = _param((self.hq + 2 * self.hkv) * self.hd, args.dim, device=device)
         self.wo = _param(args.dim, self.hq * self.hd, device=device)
@@ -92,9 +94,10 @@ class LlamaAttention(torch.nn.Module):
         bs = qkv.shape[0]
         qkv = qkv.view(bs, self.hq + 2 * self.hkv, self.hd)
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
-        # RoPE(q, k) + append of k and v to their pages: one launch
-        q = ops.gqa_qkv_post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, self.cache.get_gpu_block_table(),
-                             self.cache.get_gpu_seq_lens_excl_this_decode(), rotary_type=self.rotary_type)
+        # RoPE(q, k) + append of k and v to their pages: one launch (fp8 cache: with quantising stores)
+        post = ops.gqa_qkv_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_post
+        q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, self.cache.get_gpu_block_table(),
+                 self.cache.get_gpu_seq_lens_excl_this_decode(), rotary_type=self.rotary_type)
         return self.decode_from_q(q)
 
     def decode_from_q(self, q):
@@ -109,8 +112,9 @@ class LlamaAttention(torch.nn.Module):
 
     def decode_from_residual(self, x, pending, norm_weight, eps, cos, sin):
         """Small decode batches: residual add + attn_norm + wqkv projection [+ RoPE and the K / V page append when the
-        rotary pairs are interleaved] in ONE launch.  Returns (x + pending, wo(attention) before the all-reduce)."""
-        if self.rotary_type == "llama":
+        rotary pairs are interleaved] in ONE launch.  Returns (x + pending, wo(attention) before the all-reduce).  The fused
+        epilogue writes bf16 page rows: an fp8 cache takes the two-launch form of "hf-llama"."""
+        if self.rotary_type == "llama" and not self.fp8_kv:
             k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
             x, qkv = ops.bf16_linear_add_norm_qkv_post(
                 x, pending, norm_weight, eps, self.wqkv, self.hq, self.hkv, cos, sin, k_cache, v_cache,
@@ -126,7 +130,13 @@ class LlamaAttention(torch.nn.Module):
         qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
         q, k = ops.apply_rotary_pos_emb(qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv], cos, sin, rotary_type=self.rotary_type)
         v = qkv[:, self.hq + self.hkv :].contiguous()
-        self.cache.finalize_cache_bylayer_prefill(k, v, self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
+        if self.fp8_kv:
+            # the pages take the quantised rows (the same index_copy_ scatter, over byte rows); attention runs over the
+            # unquantised ones, as the MLA prefill does
+            self.cache.finalize_cache_bylayer_prefill(ops.gqa_kv_quant_fp8(k), ops.gqa_kv_quant_fp8(v), self.cache.curr_req_ids,
+                                                      self.cache.curr_varlens, self.layer_id)
+        else:
+            self.cache.finalize_cache_bylayer_prefill(k, v, self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
         o = self.attn_backend.attn_varlen_func(q, k, v, varlens.prefix_lens, varlens.prefix_lens, varlens.max_len,
                                                varlens.max_len, causal=True)
         return ops.bf16_linear(o.reshape(T, self.hq * self.hd), self.wo)
@@ -189,6 +199,17 @@ class LlamaDecoder(torch.nn.Module):
         self.args, self.cache, self.attn_backend, self.device = args, cache, attn_backend, torch.device(device)
         t = tp.get_tp_size()
         assert args.vocab_size % t == 0 and args.n_kv_heads % t == 0 and args.head_dim == 128, "gqa_decode: head_dim 128"
+        # the cache this decoder was handed must have the format its args name (gqa_kv_layout raises on an unknown name)
+        # in both modes: a bf16 cache of another row shape or dtype used to fail at the first attention assert, it fails here now.
+        # cache None is a decoder that only holds weights (checkpoint loading and conversion build one); it never attends.
+        kv_shape, kv_dtype = gqa_kv_layout(args.kv_cache_dtype, args.n_kv_heads // t, args.head_dim)
+        if cache is not None:
+            got = [(tuple(c.shape[3:]), c.dtype) for c in (cache.paged_k_cache, cache.paged_v_cache)]
+            if not all(g == (tuple(kv_shape), kv_dtype) for g in got):
+                raise ValueError(
+                    f"kv_cache_dtype={args.kv_cache_dtype!r} needs K and V caches of {tuple(kv_shape)} x {kv_dtype} per token, got {got}: build "
+                    "the cache with PagedKVCacheManager(k_shape_per_sample=shape, v_shape_per_sample=shape, dtype=dtype), "
+                    "(shape, dtype) = cache_manager.gqa_kv_layout(kv_cache_dtype, n_local_kv_heads)")
         self.vocab_local = args.vocab_size // t
         self.vocab_start = tp.get_tp_rank() * self.vocab_local
         self.embed_weight = _param(self.vocab_local, args.dim, device=device)

@@ -32,6 +32,7 @@ class MixtralArgs:
     rope_theta: float = 1000000.0
     num_local_experts: int = 8
     num_experts_per_tok: int = 2
+    kv_cache_dtype: str = "bf16"  # "fp8": see LlamaArgs.kv_cache_dtype
 
     @property
     def head_dim(self):

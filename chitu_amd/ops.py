@@ -287,6 +287,72 @@ def append_mla_kv_fp8(kv_cache, page_table, this_kv, old_seq_lens):
     )
 
 
+GQA_KV_FP8_ROW = 144  # bytes of one (token, kv head) of the fp8 K / V cache (csrc/gqa_kv_fp8.hip; cache_manager.gqa_kv_layout("fp8"))
+
+
+def _heads128(x):
+    """bf16 [T, Hkv, 128] rows the fp8 K / V kernels can read in place: dense heads, row stride a multiple of 8 elements,
+    16-byte aligned (the k / v slices of a merged qkv projection are); anything else is copied."""
+    assert x.dtype == torch.bfloat16 and x.dim() == 3 and x.shape[2] == 128
+    ok = x.stride(2) == 1 and x.stride(1) == 128 and x.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] * 128 and x.data_ptr() % 16 == 0
+    return x if ok or x.shape[0] == 0 else x.contiguous()
+
+
+def gqa_kv_quant_fp8(x, out=None):
+    """bf16 [T, Hkv, 128] (row-strided views allowed) -> uint8 [T, Hkv, 144] rows of the fp8 K / V cache: per head 128 e4m3
+    codes | one fp32 power-of-two scale | 12 zero bytes.  out: a uint8 [T, Hkv, 144] destination with dense heads and a row
+    stride that is a multiple of 16 bytes."""
+    require_cuda(x, out)
+    x = _heads128(x)
+    T, H, _ = x.shape
+    if out is None:
+        out = torch.empty(T, H, GQA_KV_FP8_ROW, dtype=torch.uint8, device=x.device)
+    assert out.dtype == torch.uint8 and tuple(out.shape) == (T, H, GQA_KV_FP8_ROW) and out.stride(2) == 1
+    assert out.stride(1) == GQA_KV_FP8_ROW or H == 1
+    check(_lib.lib().chitu_hip_gqa_kv_quant_fp8(ptr(x), i64(x.stride(0)), ptr(out), i64(out.stride(0)), i64(T), i32(H), stream_ptr()),
+          "gqa_kv_quant_fp8")
+    return out
+
+
+def gqa_kv_dequant_fp8(rows):
+    """The inverse of gqa_kv_quant_fp8: uint8 [..., Hkv, 144] rows (a whole cache included) -> bf16 [..., Hkv, 128].  Exact: every
+    code x scale product is a bf16 number."""
+    require_cuda(rows)
+    assert rows.dtype == torch.uint8 and rows.dim() >= 2 and rows.shape[-1] == GQA_KV_FP8_ROW and rows.is_contiguous()
+    H = rows.shape[-2]
+    T = rows.numel() // (H * GQA_KV_FP8_ROW)
+    out = torch.empty(*rows.shape[:-1], 128, dtype=torch.bfloat16, device=rows.device)
+    check(_lib.lib().chitu_hip_gqa_kv_dequant_fp8(ptr(rows), i64(H * GQA_KV_FP8_ROW), ptr(out), i64(T), i32(H), stream_ptr()),
+          "gqa_kv_dequant_fp8")
+    return out
+
+
+def _check_gqa_fp8_caches(k_cache, v_cache):
+    assert k_cache.dtype == torch.uint8 and v_cache.dtype == torch.uint8 and k_cache.dim() == 4 and k_cache.shape == v_cache.shape
+    assert k_cache.shape[-1] == GQA_KV_FP8_ROW and k_cache.is_contiguous() and v_cache.is_contiguous()
+
+
+def append_gqa_kv_fp8(k_cache, v_cache, page_table, this_k, this_v, old_seq_lens):
+    """append_to_paged_kv_cache for the fp8 K / V caches, both in one launch: row i of this_k / this_v (bf16 [bs, Hkv, 128] or
+    [bs, 1, Hkv, 128]) is quantised (gqa_kv_quant_fp8's bytes) into cache[page_table[i][L_i // page]][L_i % page], caches uint8
+    [pages, page, Hkv, 144].  An out-of-range table entry, a negative length or a position beyond the table writes nothing."""
+    require_cuda(k_cache, v_cache, page_table, this_k, this_v, old_seq_lens)
+    _check_gqa_fp8_caches(k_cache, v_cache)
+    assert page_table.dtype == torch.int32 and old_seq_lens.dtype == torch.int32
+    assert page_table.dim() == 2 and page_table.is_contiguous() and old_seq_lens.is_contiguous()
+    bs, H = this_k.shape[0], k_cache.shape[2]  # the table may hold more rows than the batch, as for gqa_qkv_post_kv_fp8
+    assert page_table.shape[0] >= bs and old_seq_lens.shape[0] >= bs and this_v.shape[0] == bs
+    k, v = (_heads128(t.reshape(bs, H, 128) if t.dim() == 4 else t) for t in (this_k, this_v))
+    assert k.shape[1] == H and v.shape[1] == H
+    check(
+        _lib.lib().chitu_hip_gqa_kv_append_fp8(
+            ptr(k), i64(k.stride(0)), ptr(v), i64(v.stride(0)), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]),
+            i32(k_cache.shape[1]), i32(H), ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), stream_ptr(),
+        ),
+        "append_gqa_kv_fp8",
+    )
+
+
 def apply_rotary_pos_emb_torch(q, k, cos, sin, rotary_type="hf-llama"):
     """Name kept for source compatibility with chitu/ops.py:243-308; runs the HIP kernel."""
     return apply_rotary_pos_emb(q, k, cos, sin, rotary_type=rotary_type)
@@ -468,6 +534,28 @@ def gqa_qkv_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table,
             ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), stream_ptr(),
         ),
         "gqa_qkv_post",
+    )
+    return qkv[:, :q_heads]
+
+
+def gqa_qkv_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, rotary_type="llama"):
+    """gqa_qkv_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): RoPE(q in place, k), the rotated k rounded
+    to bf16 as gqa_qkv_post rounds it and quantised, v quantised, both written straight into their page rows -- the bytes of
+    gqa_kv_quant_fp8 on the rows gqa_qkv_post writes.  One launch; returns the q view."""
+    require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[1] == q_heads + 2 * kv_heads
+    _check_gqa_fp8_caches(k_cache, v_cache)
+    assert k_cache.shape[2] == kv_heads and qkv.shape[2] == 128 and page_table.dtype == torch.int32 and page_table.stride(1) == 1
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and old_seq_lens.dtype == torch.int32
+    bs, _, d = qkv.shape
+    assert cos.shape == (bs, d // 2) and page_table.shape[0] >= bs and page_table.is_contiguous()
+    check(
+        _lib.lib().chitu_hip_gqa_qkv_post_kv_fp8(
+            ptr(qkv), i64(qkv.stride(0)), i32(q_heads), i32(kv_heads), i32(d), ptr(cos), ptr(sin),
+            i32(0 if rotary_type == "llama" else 1), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
+            ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), stream_ptr(),
+        ),
+        "gqa_qkv_post_kv_fp8",
     )
     return qkv[:, :q_heads]
 

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 6  /* 6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 7  /* 7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -758,6 +758,51 @@ int chitu_hip_gqa_decode(const void* q_bf16, int64_t q_stride_b, int64_t q_strid
                          float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads,
                          int32_t head_dim, int32_t num_splits, void* workspace, int64_t workspace_bytes,
                          void* stream);
+
+/* ---- FP8 K / V cache of the GQA / MHA paged decode (csrc/gqa_kv_fp8.hip, csrc/gqa_decode_kv_fp8.hip) --------
+ * K and V stay two caches of the shape above with byte rows: uint8 [num_pages, page_size, kv_heads, 144], base 16-byte aligned.
+ * One (token, kv head) row: [0, 128) the head's channels as OCP e4m3fn codes, order unchanged | [128, 132) one fp32 scale, an
+ * exact power of two | [132, 144) zero, written by every producer and read by nobody.  amax = max|x| over the head, e = the
+ * smallest integer with amax <= 448 * 2^e clamped to e >= -64 (amax == 0: -64), scale = 2^e, code = RNE_e4m3(x * 2^-e) (never
+ * overflows; the rule of the MLA cache above); NaN / Inf inputs are unspecified.  code * scale is a bf16 number: dequantisation
+ * is exact.  head_dim 128 only.
+ *   chitu_hip_gqa_kv_quant_fp8    new: no reference counterpart.  src bf16 [rows, kv_heads, 128] with a row stride in elements
+ *     (>= kv_heads * 128, % 8, base 16-byte aligned) -> dst bytes [rows, kv_heads, 144] with a row stride in bytes
+ *     (>= kv_heads * 144, % 16, base 16-byte aligned); bytes of a destination row beyond kv_heads * 144 are not written.
+ *   chitu_hip_gqa_kv_dequant_fp8  new: no reference counterpart.  The inverse: byte rows (stride as above) -> bf16
+ *     [rows, kv_heads, 128] contiguous.  Exact.
+ *   chitu_hip_gqa_kv_append_fp8   new: no reference counterpart.  Quantises row b of k and of v (bf16 [batch, kv_heads, 128],
+ *     row strides in elements) into position old_seq_lens[b] of sequence b's page in k_cache and in v_cache:
+ *     cache[table[b][L / page_size]][L % page_size], one launch.  Any page_size >= 1.  A table entry outside [0, num_pages), a
+ *     negative length or a position beyond pages_per_seq writes nothing (the rules of chitu_hip_append_paged_kv).
+ *   chitu_hip_gqa_qkv_post_kv_fp8 new: no reference counterpart.  chitu_hip_gqa_qkv_post's argument list with byte-row caches:
+ *     RoPE on q in place and on k, the rotated k rounded to bf16 exactly as chitu_hip_gqa_qkv_post rounds it and then
+ *     quantised, v quantised, both written straight into the page rows -- bit for bit the quantiser's image of the rows
+ *     chitu_hip_gqa_qkv_post writes.  Both rotary layouts; head_dim 128.
+ *   chitu_hip_gqa_decode_kv_fp8   new: no reference counterpart.  chitu_hip_gqa_decode's argument list and contract (grid, split
+ *     arithmetic, workspace layout, limits) with k_cache / v_cache reading 144-byte rows.  q stays bf16; codes are widened to
+ *     bf16 in registers (exact) and everything behind that is chitu_hip_gqa_decode's arithmetic in its order: the output, and
+ *     with num_splits > 1 the workspace, are bit-identical to chitu_hip_gqa_decode on the dequantised cache.  Bytes past a
+ *     sequence's length are never used, whatever they hold. */
+int chitu_hip_gqa_kv_quant_fp8(const void* src_bf16, int64_t src_stride, void* dst_u8, int64_t dst_stride_bytes,
+                               int64_t rows, int32_t kv_heads, void* stream);
+int chitu_hip_gqa_kv_dequant_fp8(const void* src_u8, int64_t src_stride_bytes, void* dst_bf16, int64_t rows,
+                                 int32_t kv_heads, void* stream);
+int chitu_hip_gqa_kv_append_fp8(const void* k_bf16, int64_t k_stride, const void* v_bf16, int64_t v_stride,
+                                void* k_cache_u8, void* v_cache_u8, int64_t num_pages, int32_t page_size,
+                                int32_t kv_heads, const int32_t* block_table, int32_t pages_per_seq,
+                                const int32_t* old_seq_lens, int32_t batch, void* stream);
+int chitu_hip_gqa_qkv_post_kv_fp8(void* qkv_bf16, int64_t row_stride, int32_t q_heads, int32_t kv_heads,
+                                  int32_t head_dim, const float* cos, const float* sin, int32_t layout,
+                                  void* k_cache_u8, void* v_cache_u8, int64_t num_pages, int32_t page_size,
+                                  const int32_t* page_table, int32_t pages_per_seq,
+                                  const int32_t* old_seq_lens, int32_t batch, void* stream);
+int chitu_hip_gqa_decode_kv_fp8(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_h, const void* k_cache,
+                                const void* v_cache, int64_t num_pages, int32_t page_size, int32_t kv_heads,
+                                const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                                float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads,
+                                int32_t head_dim, int32_t num_splits, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 
 /* ---- token sampling (the step after the path) -----------------------------------
  * Replaces NormalExecutor.update_response's device work (chitu/executor.py:82-112) and
