@@ -63,10 +63,14 @@ def _num_cus():
         return 256
 
 
-def gqa_num_splits(batch: int, kv_heads: int, max_pages: int, page_size: int) -> int:
+def gqa_num_splits(batch: int, kv_heads: int, max_pages: int, page_size: int, window_left: int = -1) -> int:
     """KV splits attn_with_kvcache gives the GQA decode launch when the caller names none: graph-static (the page table's
-    width, not the lengths), never more than 16-token steps, the cap above, and _GQA_WAVES_PER_CU workgroups per CU."""
+    width, not the lengths), never more than 16-token steps, the cap above, and _GQA_WAVES_PER_CU workgroups per CU.
+    window_left >= 0: a sequence walks at most the steps that overlap W + 1 keys ((W + 16) // 16 + 1 of them), so a short
+    window is not cut into splits that have nothing to do."""
     max_steps = max(1, max_pages * page_size // 16)
+    if window_left >= 0:
+        max_steps = min(max_pages * page_size, window_left + 16) // 16 + 1
     return max(1, min(max_steps, _GQA_MAX_SPLITS, (_GQA_WAVES_PER_CU * _num_cus()) // max(1, batch * kv_heads)))
 
 
@@ -83,6 +87,27 @@ def choose_num_splits(batch: int, head_blocks: int, max_tiles: int, target_wgs: 
     per = max(1, batch * head_blocks)
     s = max(1, min(max_tiles, (target_wgs + per - 1) // per))
     return min(s, 64)
+
+
+def window_and_cap(window_size, softcap, causal: bool):
+    """(window_left, softcap) of the reference's window_size / softcap arguments (attn_backend.py:55-69) in the forms the GQA
+    kernels implement: a left window W >= 0 (-1: none) whose effective right side is 0 -- given as 0, or implied by causal=True,
+    which makes the reference set it to 0 (RefAttnBackend._attention, :333-334) -- and softcap >= 0.  (-1, -1) is no window.
+    Anything else raises."""
+    left, right = (int(w) for w in window_size)
+    softcap = float(softcap)
+    if not softcap >= 0.0:
+        raise ValueError(f"softcap={softcap}: must be >= 0 (0.0 = off)")
+    if left < -1 or right < -1:
+        raise ValueError(f"window_size={window_size}: -1 means unlimited, anything below is not a window")
+    if causal:
+        right = 0
+    if (left, right) == (-1, -1):
+        return -1, softcap
+    if right != 0:
+        raise NotImplementedError(f"window_size={tuple(window_size)} with causal={causal}: only a left window (right side 0, given or "
+                                  "implied by causal=True) is implemented")
+    return left, softcap
 
 
 _tickets = {}
@@ -305,12 +330,16 @@ class HipAttnBackend(AttnBackend):
         (keys staged into 64-token pages, every query token run as one decode "sequence" over them) -- equal to "exact"
         bit for bit, KV re-read once per token.
         No host sync; not graph-captured (prefill never is, model.py:538-546)."""
-        assert causal and dropout_p == 0.0 and tuple(window_size) == (-1, -1) and softcap == 0.0
-        require_cuda(q, k, cu_seqlens_q, cu_seqlens_k)
+        assert causal and dropout_p == 0.0
         T, H, Dq = q.shape
         C, R = self.kv_lora_rank, self.qk_rope_head_dim
         if Dq == 128 and k.dim() == 3 and k.shape[-1] == 128 and tuple(v.shape) == tuple(k.shape):
-            return self._gqa_varlen_causal(q, k, v, cu_seqlens_k, int(max_seqlen_k), softmax_scale)
+            # GQA / MHA, head_dim 128: window_size = (W, r) (causal: r is 0 whatever was given) and softcap >= 0 are implemented
+            window_left, softcap = window_and_cap(window_size, softcap, causal)
+            require_cuda(q, k, cu_seqlens_q, cu_seqlens_k)
+            return self._gqa_varlen_causal(q, k, v, cu_seqlens_k, int(max_seqlen_k), softmax_scale, window_left, softcap)
+        assert tuple(window_size) == (-1, -1) and softcap == 0.0, "not used by the MLA prefill path"
+        require_cuda(q, k, cu_seqlens_q, cu_seqlens_k)
         assert Dq == C + R and tuple(k.shape) == (T, 1, Dq) and v.shape[0] == T and v.shape[-1] == C, \
             "only the MLA absorb-mode MQA shape (q/k 576, v 512) is implemented"
         assert cu_seqlens_q.shape == cu_seqlens_k.shape and max_seqlen_q == max_seqlen_k
@@ -361,13 +390,14 @@ class HipAttnBackend(AttnBackend):
                             softmax_scale, num_splits=1, out=out[t0:t1])
         return out
 
-    def _gqa_varlen_causal(self, q, k, v, cu_seqlens, max_seqlen, softmax_scale):
+    def _gqa_varlen_causal(self, q, k, v, cu_seqlens, max_seqlen, softmax_scale, window_left=-1, softcap=0.0):
         """Causal GQA / MHA prefill attention (Attention.prefill_forward, models/model.py:104-132), head_dim 128:
         q [T, Hq, 128], k / v [T, Hkv, 128].  Default: the flash kernel chitu_hip_gqa_prefill.  CHITU_GQA_PREFILL=compose
         (and shapes the kernel does not take): the round-2 composition from the decode kernel -- keys / values staged once
         into 256-token pages, every query token one decode "sequence" of length pos + 1 over its own sequence's pages
         (chitu_hip_gqa_decode): exact causal attention with the decode numerics, KV re-read once per query token; kept
-        as the cross-check.  No host sync either way."""
+        as the cross-check.  window_left >= 0 (a token sees itself and the window_left before it) or softcap > 0:
+        chitu_hip_gqa_prefill_window; the composition passes both on to the windowed decode launch.  No host sync either way."""
         T, Hq, D = q.shape
         Hkv = k.shape[1]
         if T == 0:
@@ -386,10 +416,13 @@ class HipAttnBackend(AttnBackend):
             out = torch.empty(T, Hq, D, dtype=torch.bfloat16, device=dev)
             if softmax_scale is None:
                 softmax_scale = D ** -0.5
-            check(_lib.lib().chitu_hip_gqa_prefill(
-                ptr(qq), i64(qq.stride(0)), i64(qq.stride(1)), ptr(kk), i64(kk.stride(0)), i64(kk.stride(1)), ptr(vv),
-                i64(vv.stride(0)), i64(vv.stride(1)), ptr(cu32), i32(cu32.numel() - 1), i32(int(max_seqlen)), f32(softmax_scale),
-                ptr(out), i32(Hq), i32(Hkv), i32(D), stream_ptr()), "gqa_prefill")
+            args = (ptr(qq), i64(qq.stride(0)), i64(qq.stride(1)), ptr(kk), i64(kk.stride(0)), i64(kk.stride(1)), ptr(vv),
+                    i64(vv.stride(0)), i64(vv.stride(1)), ptr(cu32), i32(cu32.numel() - 1), i32(int(max_seqlen)), f32(softmax_scale),
+                    ptr(out), i32(Hq), i32(Hkv), i32(D))
+            if window_left >= 0 or softcap > 0.0:
+                check(_lib.lib().chitu_hip_gqa_prefill_window(*args, i32(window_left), f32(softcap), stream_ptr()), "gqa_prefill_window")
+            else:
+                check(_lib.lib().chitu_hip_gqa_prefill(*args, stream_ptr()), "gqa_prefill")
             return out
         page = 256
         n_seq = cu_seqlens.numel() - 1
@@ -413,7 +446,8 @@ class HipAttnBackend(AttnBackend):
         for t0 in range(0, T, step):
             t1 = min(T, t0 + step)
             out[t0:t1] = self.attn_with_kvcache(q[t0:t1].unsqueeze(1), k_pages, v_pages, None, None, cache_seqlens=lens[t0:t1].contiguous(),
-                                                block_table=table[t0:t1].contiguous(), softmax_scale=softmax_scale).view(t1 - t0, Hq, D)
+                                                block_table=table[t0:t1].contiguous(), window_size=(window_left, 0), softcap=softcap,
+                                                softmax_scale=softmax_scale).view(t1 - t0, Hq, D)
         return out
 
     # ------------------------------------------------------------------ non-MLA (GQA / MHA) paged decode
@@ -445,9 +479,15 @@ class HipAttnBackend(AttnBackend):
         k_cache / v_cache uint8 [pages, page_size, Hkv, 144] (the fp8 K / V cache): k / v are quantised as they are appended
         (ops.append_gqa_kv_fp8, one launch for both) and chitu_hip_gqa_decode_kv_fp8 reads the pages -- same arguments, same
         workspace; the result is bit-identical to this call on ops.gqa_kv_dequant_fp8 of the caches.
+
+        window_size = (W, 0) -- or (W, r) with causal=True, which makes the right side 0 -- and softcap >= 0 (the reference's
+        semantics, :136-138 and RefAttnBackend._attention): the query sees the last W + 1 keys, the appended one included, and
+        the score is softcap * tanh(scale * q.k / softcap).  chitu_hip_gqa_decode_window / _kv_fp8_window, taken only when a
+        window or a cap is set; they read only the pages the window overlaps.  A right window on a non-causal call raises.
         """
         assert block_table is not None, "HipAttnBackend.attn_with_kvcache is the paged path"
-        assert cache_leftpad is None and window_size == (-1, -1) and softcap == 0.0
+        assert cache_leftpad is None, "cache_leftpad is not implemented"
+        window_left, softcap = window_and_cap(window_size, softcap, causal)
         assert q.dim() == 4 and q.shape[1] == 1, "decode: one query token per sequence"
         require_cuda(q, k_cache, v_cache, cache_seqlens, block_table)
         fp8_kv = is_fp8_gqa_cache(k_cache)
@@ -474,18 +514,21 @@ class HipAttnBackend(AttnBackend):
         if not (q3.stride(-1) == 1 and q3.stride(0) % 8 == 0 and q3.stride(1) % 8 == 0 and q3.data_ptr() % 16 == 0):
             q3 = q3.contiguous()
         if num_splits is None:
-            num_splits = gqa_num_splits(bs, Hkv, int(block_table.shape[1]), int(k_cache.shape[1]))
+            num_splits = gqa_num_splits(bs, Hkv, int(block_table.shape[1]), int(k_cache.shape[1]), window_left)
         out = torch.empty(bs, Hq, D, dtype=torch.bfloat16, device=q.device)
         need = bs * Hq * num_splits * (D + 1) * 4 if num_splits > 1 else 1
         ws = workspace.get(need, q.device, "gqa")
-        entry = _lib.lib().chitu_hip_gqa_decode_kv_fp8 if fp8_kv else _lib.lib().chitu_hip_gqa_decode
+        name = "gqa_decode_kv_fp8" if fp8_kv else "gqa_decode"
+        extra = ()
+        if window_left >= 0 or softcap > 0.0:
+            name, extra = name + "_window", (i32(window_left), f32(softcap))
         check(
-            entry(
+            getattr(_lib.lib(), "chitu_hip_" + name)(
                 ptr(q3), i64(q3.stride(0)), i64(q3.stride(1)), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]),
                 i32(k_cache.shape[1]), i32(Hkv), ptr(block_table), i32(block_table.stride(0)), ptr(seqlens),
                 f32(softmax_scale), ptr(out), i32(bs), i32(Hq), i32(D), i32(num_splits), ptr(ws), i64(ws.numel()),
-                stream_ptr(),
+                *extra, stream_ptr(),
             ),
-            "gqa_decode_kv_fp8" if fp8_kv else "gqa_decode",
+            name,
         )
         return out.view(bs, 1, Hq, D)

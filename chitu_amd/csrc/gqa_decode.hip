@@ -91,5 +91,19 @@ extern "C" int chitu_hip_gqa_decode(const void* q_bf16, int64_t q_stride_b, int6
                                     void* stream) {
     return chitu::gqa_decode_launch<false>(q_bf16, q_stride_b, q_stride_h, k_cache, v_cache, num_pages, page_size, kv_heads,
                                            block_table, table_stride, seqlens, softmax_scale, out_bf16, batch, q_heads, head_dim,
-                                           num_splits, workspace, workspace_bytes, stream);
+                                           num_splits, workspace, workspace_bytes, -1, 0.0f, stream);
+}
+
+// Sliding-window / soft-capped form (gqa_decode_tile.h, kWin): FlashAttnBackend.attn_with_kvcache's window_size = (W, 0) and
+// softcap (chitu/attn_backend.py:208-243, contract :92-164; RefAttnBackend._attention :294-392 is the arithmetic).
+extern "C" int chitu_hip_gqa_decode_window(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_h,
+                                           const void* k_cache, const void* v_cache, int64_t num_pages,
+                                           int32_t page_size, int32_t kv_heads, const int32_t* block_table,
+                                           int32_t table_stride, const int32_t* seqlens, float softmax_scale,
+                                           void* out_bf16, int32_t batch, int32_t q_heads, int32_t head_dim,
+                                           int32_t num_splits, void* workspace, int64_t workspace_bytes,
+                                           int32_t window_left, float softcap, void* stream) {
+    return chitu::gqa_decode_launch<false>(q_bf16, q_stride_b, q_stride_h, k_cache, v_cache, num_pages, page_size, kv_heads,
+                                           block_table, table_stride, seqlens, softmax_scale, out_bf16, batch, q_heads, head_dim,
+                                           num_splits, workspace, workspace_bytes, window_left, softcap, stream);
 }

@@ -8,6 +8,14 @@
 //                image.  Everything from the first MFMA on is one code path, so the output -- and the workspace partials -- are
 //                bit-identical to the bf16 kernel on the dequantised cache at the same num_splits.  No LDS pass and no barrier
 //                is added; K is widened where the bf16 form copies its prefetched fragments, V where it stores them to the slab.
+//
+// kWin == true : the sliding-window / soft-capped form of either (chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window;
+//                the reference's semantics, attn_backend.py:55-69 / RefAttnBackend._attention :294-392).  window_left = W >= 0:
+//                the query (position L - 1) sees the keys w0 = max(0, L - 1 - W) .. L - 1.  The wave walks the 16-token steps
+//                [w0 >> 4, n16) only, divided among the splits as [0, n16) is without a window; keys below w0 in the first step
+//                are masked like the keys past the end (score -inf, V row staged as zeros, K re-reads a row of the window), and a
+//                page wholly before the window is never named.  softcap = c > 0: score = c * tanh(scale * q.k / c).  With both
+//                neutral the launcher takes the kWin == false kernel, which is the code it was before this form existed.
 #pragma once
 #include <type_traits>
 
@@ -24,12 +32,13 @@ typedef short s16x4g __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4g;
 
 // grid (num_splits, batch * kv_heads); block 64.
-template <bool kFp8>
+template <bool kFp8, bool kWin = false>
 __global__ __launch_bounds__(64) void gqa_decode_kernel(
     const bf16_t* __restrict__ q, int64_t q_sb, int64_t q_sh, const std::conditional_t<kFp8, uint8_t, bf16_t>* __restrict__ kc,
     const std::conditional_t<kFp8, uint8_t, bf16_t>* __restrict__ vc, int64_t num_pages, int page_size, int Hkv,
     const int32_t* __restrict__ table, int table_stride, const int32_t* __restrict__ seqlens, float scale,
-    float* __restrict__ part_o, float* __restrict__ part_lse, bf16_t* __restrict__ out, int Hq, int num_splits) {
+    float* __restrict__ part_o, float* __restrict__ part_lse, bf16_t* __restrict__ out, int Hq, int num_splits, int window_left,
+    float softcap) {
     constexpr int kRow = kFp8 ? kGqaKvFp8Row : kHd;  // elements (fp8: bytes) of one (token, kv head) row
     __shared__ __attribute__((aligned(16))) uint8_t vlds[16 * kVRowB];
     const int lane = threadIdx.x, j = lane & 15, g = lane >> 4;
@@ -39,8 +48,13 @@ __global__ __launch_bounds__(64) void gqa_decode_kernel(
     const int n16 = (L + 15) >> 4;
     // 32-bit unsigned quotients: a 64-bit division is a software loop on the kernel's critical chain (the launcher bounds
     // 16-token steps x splits below 2^31)
-    const int s0i = (int)((unsigned)n16 * (unsigned)split / (unsigned)num_splits);
-    const int s1i = (int)((unsigned)n16 * (unsigned)(split + 1) / (unsigned)num_splits);
+    // kWin: the first visible key and its step (L - 1 - W cannot wrap: L >= 0, W <= 2^31 - 1); 0 without a window
+    const int w0 = kWin && window_left >= 0 ? max(L - 1 - window_left, 0) : 0;
+    const int f16 = w0 >> 4;
+    int s0i = (int)((unsigned)(n16 - f16) * (unsigned)split / (unsigned)num_splits);
+    int s1i = (int)((unsigned)(n16 - f16) * (unsigned)(split + 1) / (unsigned)num_splits);
+    if constexpr (kWin) s0i += f16, s1i += f16;
+    const float cap_inv = kWin && softcap > 0.f ? 1.0f / softcap : 0.f;
     const int32_t* tbl = table + (int64_t)b * table_stride;
     const int64_t tok_stride = (int64_t)Hkv * kRow;
 
@@ -65,7 +79,8 @@ __global__ __launch_bounds__(64) void gqa_decode_kernel(
         int64_t page = tbl[t0 / page_size];
         if (page < 0 || page >= num_pages) page = 0;
         const int64_t base = (page * page_size + (t0 % page_size)) * tok_stride + (int64_t)kvh * kRow;
-        const int tk = min(j, L - 1 - t0);  // rows past the end re-read the last valid row (masked below)
+        // rows past the end re-read the last valid row, kWin: rows before the window its first row, w0 <= L - 1 (masked below)
+        const int tk = kWin ? max(min(j, L - 1 - t0), w0 - t0) : min(j, L - 1 - t0);
         if constexpr (kFp8) {
             const uint8_t* krow = kc + base + (int64_t)max(tk, 0) * tok_stride;
 #pragma unroll
@@ -77,7 +92,7 @@ __global__ __launch_bounds__(64) void gqa_decode_kernel(
                 // V rows past the end are staged as zeros (0 * garbage must stay 0): code 0 x scale 1, whatever the bytes hold
                 vr[i] = i32x2{0, 0};
                 vs[i] = 1.f;
-                if (t0 + row < L) {
+                if (t0 + row < L && (!kWin || t0 + row >= w0)) {  // nor the rows before the window
                     const uint8_t* vrow = vc + base + (int64_t)row * tok_stride;
                     vr[i] = *reinterpret_cast<const i32x2*>(vrow + col * 8);
                     vs[i] = *reinterpret_cast<const float*>(vrow + kGqaKvFp8ScaleOff);
@@ -91,7 +106,8 @@ __global__ __launch_bounds__(64) void gqa_decode_kernel(
             for (int i = 0; i < 4; ++i) {
                 const int c = lane + i * 64, row = c >> 4, col = c & 15;
                 vr[i] = i32x4{0, 0, 0, 0};  // V rows past the end are staged as zeros (0 * garbage must stay 0)
-                if (t0 + row < L) vr[i] = *reinterpret_cast<const i32x4*>(vc + base + (int64_t)row * tok_stride + col * 8);
+                if (t0 + row < L && (!kWin || t0 + row >= w0))  // nor the rows before the window
+                    vr[i] = *reinterpret_cast<const i32x4*>(vc + base + (int64_t)row * tok_stride + col * 8);
             }
         }
     };
@@ -120,7 +136,17 @@ __global__ __launch_bounds__(64) void gqa_decode_kernel(
         float sv[4], mx = -INFINITY;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            sv[r] = (t0 + g * 4 + r) < L ? s[r] * scale : -INFINITY;
+            if constexpr (kWin) {
+                float x = s[r] * scale;
+                if (softcap > 0.f) {  // c * tanh(x / c), tanh(y) = 1 - 2 / (1 + e^2y); |y| <= 15 keeps e^2y finite, tanh(15) rounds to 1
+                    const float y = __builtin_fminf(__builtin_fmaxf(x * cap_inv, -15.f), 15.f);
+                    x = softcap * (1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * y)));
+                }
+                const int t = t0 + g * 4 + r;
+                sv[r] = t >= w0 && t < L ? x : -INFINITY;
+            } else {
+                sv[r] = (t0 + g * 4 + r) < L ? s[r] * scale : -INFINITY;
+            }
             mx = __builtin_fmaxf(mx, sv[r]);
         }
         float al[4] = {1.f, 1.f, 1.f, 1.f};
@@ -181,16 +207,19 @@ __global__ __launch_bounds__(64) void gqa_decode_kernel(
 void launch_gqa_merge(const float* part_o, const float* part_lse, bf16_t* out, int64_t bh, int num_splits, hipStream_t st);
 
 // The argument checks, the workspace carve-up and the two launches of chitu_hip_gqa_decode / chitu_hip_gqa_decode_kv_fp8.
+// window_left = -1 and softcap = 0 (what the two plain entries pass): the kernel without the window / cap code.
 template <bool kFp8>
 static inline int gqa_decode_launch(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_h, const void* k_cache,
                                     const void* v_cache, int64_t num_pages, int32_t page_size, int32_t kv_heads,
                                     const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
                                     float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads, int32_t head_dim,
-                                    int32_t num_splits, void* workspace, int64_t workspace_bytes, void* stream) {
+                                    int32_t num_splits, void* workspace, int64_t workspace_bytes, int32_t window_left,
+                                    float softcap, void* stream) {
     using cache_t = std::conditional_t<kFp8, uint8_t, bf16_t>;
     CHITU_REQUIRE(q_bf16 && k_cache && v_cache && block_table && seqlens && out_bf16);
     CHITU_REQUIRE(batch >= 0 && q_heads >= 1 && kv_heads >= 1 && num_pages >= 1 && table_stride >= 1);
     CHITU_REQUIRE(q_heads % kv_heads == 0 && num_splits >= 1 && num_splits <= 256);
+    CHITU_REQUIRE(window_left >= -1 && softcap >= 0.f);  // (a NaN cap fails the comparison)
     if (head_dim != kHd || q_heads / kv_heads > 16) return CHITU_ERR_UNSUPPORTED;
     if (page_size < 16 || page_size % 16 != 0) return CHITU_ERR_UNSUPPORTED;
     CHITU_REQUIRE(q_stride_b % 8 == 0 && q_stride_h % 8 == 0);
@@ -207,10 +236,15 @@ static inline int gqa_decode_launch(const void* q_bf16, int64_t q_stride_b, int6
         part_lse = part_o + (int64_t)batch * q_heads * num_splits * kHd;
     }
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(gqa_decode_kernel<kFp8>, dim3((unsigned)num_splits, (unsigned)(batch * kv_heads)), dim3(64), 0, st,
-                       (const bf16_t*)q_bf16, q_stride_b, q_stride_h, (const cache_t*)k_cache, (const cache_t*)v_cache,
-                       num_pages, (int)page_size, (int)kv_heads, block_table, (int)table_stride, seqlens, softmax_scale,
-                       part_o, part_lse, (bf16_t*)out_bf16, (int)q_heads, (int)num_splits);
+    const dim3 grid((unsigned)num_splits, (unsigned)(batch * kv_heads));
+#define CHITU_GQA_DECODE_LAUNCH(WIN)                                                                                          \
+    hipLaunchKernelGGL((gqa_decode_kernel<kFp8, WIN>), grid, dim3(64), 0, st, (const bf16_t*)q_bf16, q_stride_b, q_stride_h,   \
+                       (const cache_t*)k_cache, (const cache_t*)v_cache, num_pages, (int)page_size, (int)kv_heads, block_table, \
+                       (int)table_stride, seqlens, softmax_scale, part_o, part_lse, (bf16_t*)out_bf16, (int)q_heads,           \
+                       (int)num_splits, (int)window_left, softcap)
+    if (window_left < 0 && softcap == 0.f) CHITU_GQA_DECODE_LAUNCH(false);
+    else CHITU_GQA_DECODE_LAUNCH(true);
+#undef CHITU_GQA_DECODE_LAUNCH
     if (num_splits > 1) launch_gqa_merge(part_o, part_lse, (bf16_t*)out_bf16, (int64_t)batch * q_heads, (int)num_splits, st);
     CHITU_RETURN_LAUNCH_STATUS();
 }

@@ -17,6 +17,13 @@
 // KV is read once per 128 / G query tokens (the composition this replaces -- one decode launch row per query token over
 // staged pages, attn_backend._gqa_varlen_causal of rounds 2-4 -- read it once per token).  Causal work grows with the block
 // index: blocks are issued heaviest first.
+//
+// kWin (chitu_hip_gqa_prefill_window): window_size = (W, 0) and softcap of the same call (attn_backend.py:55-69; the arithmetic of
+// RefAttnBackend._attention, :294-392).  W >= 0: query position p sees the keys p - W .. p.  A workgroup's first tile is the one
+// that holds key max(0, p0 - W) instead of tile 0 (the ring starts there), half tiles wholly below that key are skipped
+// (workgroup-uniform), and the tiles that reach below p0 - W + BQ mask per lane (key < pq - W).  A query row's first half tiles
+// can then be empty for that row: its running maximum stays -inf, which the kWin arithmetic allows for.  softcap = c > 0: the
+// score is c * tanh(scale * q.k / c), folded into log2 units after the cap.
 #include <type_traits>
 
 #include "common.h"
@@ -36,11 +43,11 @@ constexpr float kDefer = 8.0f;
 typedef float f32x16g __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_gp;
 
-template <int G>  // query heads per KV head (1 .. 32, a power of two)
+template <int G, bool kWin = false>  // G: query heads per KV head (1 .. 32, a power of two)
 __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
     const bf16_t* __restrict__ q, int64_t q_st, int64_t q_sh, const bf16_t* __restrict__ k, int64_t k_st, int64_t k_sh,
     const bf16_t* __restrict__ v, int64_t v_st, int64_t v_sh, const int32_t* __restrict__ cu_seqlens, float scale,
-    bf16_t* __restrict__ out, int Hq) {
+    bf16_t* __restrict__ out, int Hq, int window_left, float softcap) {
     using namespace gpf;
     constexpr int TPW = 32 / G;   // query tokens per wave
     constexpr int BQ = 4 * TPW;   // per workgroup
@@ -55,8 +62,12 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
     const int nq = min(BQ, L - p0);
     const int n_keys = p0 + nq;
     const int n_tiles = (n_keys + kTile - 1) / kTile;
+    const bool win = kWin && window_left >= 0;
+    const int lo = win ? max(p0 - window_left, 0) : 0;  // the block's lowest visible key
+    const int tile0 = lo / kTile;
     const int tq = wave * TPW + row / G;    // this lane's query token within the block (one past the end repeats the last, stores nothing)
-    const int pq = p0 + min(tq, nq - 1);    // its position: keys 0 .. pq
+    const int pq = p0 + min(tq, nq - 1);    // its position: keys 0 .. pq (kWin: klo .. pq)
+    const int klo = win ? pq - window_left : 0;
     const int head = kvh * G + row % G;
     const bf16_t* kbase = k + (int64_t)s0 * k_st + (int64_t)kvh * k_sh;
     const bf16_t* vbase = v + (int64_t)s0 * v_st + (int64_t)kvh * v_sh;
@@ -75,7 +86,7 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
             glds16_vaddr(vbase + grow * v_st + ((dp ^ ((r & 3) << 2)) << 3), dst + (uint32_t)(kTileB + (wave * 4 + i) * 1024));
         }
     };
-    issue(0);
+    issue(tile0);
 
     // ---- Q fragments (B operand of S^T = K Q^T): lane (row, hi) holds q[token][head][16 kk + 8 hi .. + 8]
     s16x8 qf[8];
@@ -94,6 +105,8 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
         for (int r = 0; r < 16; ++r) o[cb][r] = 0.f;
     float m = -INFINITY, l = 0.f;
     const float c2 = scale * 1.4426950408889634f;
+    const bool cap = kWin && softcap > 0.f;
+    const float cap_in = cap ? scale / softcap : 0.f, cap_out = softcap * 1.4426950408889634f;
 
     // lane-constant LDS offsets
     int koff[8];
@@ -104,17 +117,19 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) voff[cb] = (4 * hi + rr) * kRow + ((cb ^ rr) << 6) + (cl << 4) + ((lane & 1) << 3);
 
-    for (int tile = 0; tile < n_tiles; ++tile) {
+    for (int tile = tile0; tile < n_tiles; ++tile) {
         const int t0 = tile * kTile;
         glds_wait_all();   // this wave's pieces of the tile have landed
         __syncthreads();   // everyone's have; the other ring slot is no longer being read
         if (tile + 1 < n_tiles) issue(tile + 1);
         const uint8_t* bufK = smem + (tile & 1) * kBuf;
         const uint8_t* bufV = bufK + kTileB;
-        const bool last = t0 + kTile > p0;  // the tile reaches into the block's own token range (two tiles at G = 1): mask by position
+        // the tile reaches into the block's own token range (two tiles at G = 1) or, kWin, below some row's window: mask by position
+        const bool last = t0 + kTile > p0 || (win && t0 < p0 - window_left + BQ);
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb) {
             if (t0 + kb * 32 >= n_keys) break;  // the block's last key is before this half tile (workgroup-uniform)
+            if (kWin && t0 + kb * 32 + 32 <= lo) continue;  // the block's lowest visible key is behind it (workgroup-uniform)
             // ---- S^T[key 32 kb + crow(reg, hi)][Q row]
             f32x16g s;
 #pragma unroll
@@ -125,11 +140,20 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
                 s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], s, 0, 0, 0);
             }
             float pmax = -INFINITY;
-            if (last) {
+            if (kWin && cap) {  // c * tanh(x / c) in log2 units; tanh(y) = 1 - 2 / (1 + e^2y), |y| <= 15 keeps e^2y finite
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int key = t0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    s[r] = key <= pq ? s[r] * c2 : -INFINITY;
+                    const float y = __builtin_fminf(__builtin_fmaxf(s[r] * cap_in, -15.f), 15.f);
+                    const float x = cap_out * (1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * y)));
+                    s[r] = !last || (key <= pq && key >= klo) ? x : -INFINITY;
+                    pmax = __builtin_fmaxf(pmax, s[r]);
+                }
+            } else if (last) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int key = t0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                    s[r] = key <= pq && (!kWin || key >= klo) ? s[r] * c2 : -INFINITY;
                     pmax = __builtin_fmaxf(pmax, s[r]);
                 }
             } else {
@@ -141,8 +165,8 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
             }
             if (__builtin_amdgcn_ballot_w64(pmax > m + kDefer) != 0) {  // m = -inf (first block): every lane votes
                 const float mx = __builtin_fmaxf(pmax, __shfl_xor(pmax, 32, 64));
-                const float m_new = __builtin_fmaxf(m, mx);  // finite: key 0 is visible to every row
-                const float alpha = __builtin_amdgcn_exp2f(m - m_new);
+                const float m_new = __builtin_fmaxf(m, mx);  // finite: key 0 is visible to every row (kWin: -inf until the row's window)
+                const float alpha = kWin && m_new == -INFINITY ? 1.f : __builtin_amdgcn_exp2f(m - m_new);
                 m = m_new;
                 l *= alpha;
 #pragma unroll
@@ -152,10 +176,11 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
             }
             s16x8 pb[2];
             float psum = 0.f;
+            const float ms = kWin && m == -INFINITY ? 0.f : m;  // a row with no visible key yet: every p is 2^-inf = 0
 #pragma unroll
             for (int r = 0; r < 16; r += 2) {
-                const float a = __builtin_amdgcn_exp2f(s[r] - m);
-                const float b = __builtin_amdgcn_exp2f(s[r + 1] - m);
+                const float a = __builtin_amdgcn_exp2f(s[r] - ms);
+                const float b = __builtin_amdgcn_exp2f(s[r + 1] - ms);
                 psum += a + b;
                 const uint32_t pk = f32x2_to_bf16x2(a, b);
                 pb[r >> 3][r & 7] = (short)(pk & 0xffffu);
@@ -197,14 +222,17 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
 
 }  // namespace chitu
 
-extern "C" int chitu_hip_gqa_prefill(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16,
-                                     int64_t k_stride_t, int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t,
-                                     int64_t v_stride_h, const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen,
-                                     float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
-                                     void* stream) {
-    using namespace chitu;
+namespace chitu {
+
+// window_left = -1 and softcap = 0 (chitu_hip_gqa_prefill): the kernels without the window / cap code
+static int gqa_prefill_launch(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16, int64_t k_stride_t,
+                              int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t, int64_t v_stride_h,
+                              const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen, float softmax_scale, void* out_bf16,
+                              int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t window_left, float softcap,
+                              void* stream) {
     CHITU_REQUIRE(q_bf16 && k_bf16 && v_bf16 && cu_seqlens && out_bf16 && n_seq >= 0 && max_seqlen >= 0);
     CHITU_REQUIRE(q_heads >= 1 && kv_heads >= 1 && q_heads % kv_heads == 0);
+    CHITU_REQUIRE(window_left >= -1 && softcap >= 0.f);  // (a NaN cap fails the comparison)
     if (head_dim != gpf::kD) return CHITU_ERR_UNSUPPORTED;
     const int G = q_heads / kv_heads;
     if (G > 32 || (G & (G - 1)) != 0) return CHITU_ERR_UNSUPPORTED;
@@ -213,10 +241,15 @@ extern "C" int chitu_hip_gqa_prefill(const void* q_bf16, int64_t q_stride_t, int
     if (n_seq == 0 || max_seqlen == 0) return CHITU_OK;
     const int BQ = 128 / G;
     const dim3 grid((unsigned)((max_seqlen + BQ - 1) / BQ), (unsigned)n_seq, (unsigned)kv_heads);
-#define LAUNCH_G(GV)                                                                                                         \
-    hipLaunchKernelGGL((gqa_prefill_flash_kernel<GV>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q_bf16, q_stride_t, \
-                       q_stride_h, (const bf16_t*)k_bf16, k_stride_t, k_stride_h, (const bf16_t*)v_bf16, v_stride_t, v_stride_h,  \
-                       cu_seqlens, softmax_scale, (bf16_t*)out_bf16, (int)q_heads)
+#define LAUNCH_GW(GV, WIN)                                                                                                   \
+    hipLaunchKernelGGL((gqa_prefill_flash_kernel<GV, WIN>), grid, dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q_bf16,    \
+                       q_stride_t, q_stride_h, (const bf16_t*)k_bf16, k_stride_t, k_stride_h, (const bf16_t*)v_bf16, v_stride_t, \
+                       v_stride_h, cu_seqlens, softmax_scale, (bf16_t*)out_bf16, (int)q_heads, (int)window_left, softcap)
+#define LAUNCH_G(GV)                                                 \
+    do {                                                             \
+        if (window_left < 0 && softcap == 0.f) LAUNCH_GW(GV, false); \
+        else LAUNCH_GW(GV, true);                                    \
+    } while (0)
     switch (G) {
         case 1: LAUNCH_G(1); break;
         case 2: LAUNCH_G(2); break;
@@ -226,5 +259,28 @@ extern "C" int chitu_hip_gqa_prefill(const void* q_bf16, int64_t q_stride_t, int
         default: LAUNCH_G(32); break;
     }
 #undef LAUNCH_G
+#undef LAUNCH_GW
     CHITU_RETURN_LAUNCH_STATUS();
+}
+
+}  // namespace chitu
+
+extern "C" int chitu_hip_gqa_prefill(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16,
+                                     int64_t k_stride_t, int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t,
+                                     int64_t v_stride_h, const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen,
+                                     float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                                     void* stream) {
+    return chitu::gqa_prefill_launch(q_bf16, q_stride_t, q_stride_h, k_bf16, k_stride_t, k_stride_h, v_bf16, v_stride_t, v_stride_h,
+                                     cu_seqlens, n_seq, max_seqlen, softmax_scale, out_bf16, q_heads, kv_heads, head_dim, -1, 0.0f,
+                                     stream);
+}
+
+extern "C" int chitu_hip_gqa_prefill_window(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16,
+                                            int64_t k_stride_t, int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t,
+                                            int64_t v_stride_h, const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen,
+                                            float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads,
+                                            int32_t head_dim, int32_t window_left, float softcap, void* stream) {
+    return chitu::gqa_prefill_launch(q_bf16, q_stride_t, q_stride_h, k_bf16, k_stride_t, k_stride_h, v_bf16, v_stride_t, v_stride_h,
+                                     cu_seqlens, n_seq, max_seqlen, softmax_scale, out_bf16, q_heads, kv_heads, head_dim, window_left,
+                                     softcap, stream);
 }

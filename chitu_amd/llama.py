@@ -14,6 +14,7 @@ All GEMMs are the weight-streaming skinny bf16 kernel (gate.hip); the whole step
 
 import os
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 import torch.nn.functional as F
@@ -37,6 +38,10 @@ class LlamaArgs:
     norm_eps: float = 1e-5
     rope_theta: float = 500000.0
     kv_cache_dtype: str = "bf16"  # "fp8": 144-byte K / V rows per token and head (cache_manager.gqa_kv_layout), quantised as they are appended
+    # a token attends to the last `sliding_window` positions, itself included (Hugging Face's rule kv_idx > q_idx - sliding_window;
+    # Mistral-7B-v0.1: 4096); None: all of them.  Passed to the attention backend as window_size = (sliding_window - 1, 0).
+    sliding_window: Optional[int] = None
+    attn_softcap: float = 0.0  # > 0: scores are attn_softcap * tanh(score / attn_softcap) (the backend's softcap); 0.0: off
 
     @property
     def head_dim(self):
@@ -81,6 +86,11 @@ class LlamaAttention(torch.nn.Module):
         self.hd = args.head_dim
         self.hq, self.hkv = args.n_heads // t, args.n_kv_heads // t
         self.fp8_kv = args.kv_cache_dtype == "fp8"
+        if args.sliding_window is not None and args.sliding_window < 1:
+            raise ValueError(f"sliding_window={args.sliding_window}: a token attends at least to itself (None = no window)")
+        # launch constants of both attention calls: the captured decode graph holds them like any other scalar argument
+        self.window_size = (-1, -1) if args.sliding_window is None else (args.sliding_window - 1, 0)
+        self.softcap = float(args.attn_softcap)
         # merged [wq | wk | wv] rows (ColumnParallel: heads split across ranks), wo RowParallel
         self.wqkv = _param((self.hq + 2 * self.hkv) * self.hd, args.dim, device=device)
         self.wo = _param(args.dim, self.hq * self.hd, device=device)
@@ -107,7 +117,8 @@ class LlamaAttention(torch.nn.Module):
         table = self.cache.get_gpu_block_table()
         o = self.attn_backend.attn_with_kvcache(
             q.unsqueeze(1), k_cache, v_cache, None, None,
-            cache_seqlens=self.cache.get_gpu_seq_lens_incl_this_decode()[:bs], block_table=table[:bs])
+            cache_seqlens=self.cache.get_gpu_seq_lens_incl_this_decode()[:bs], block_table=table[:bs],
+            window_size=self.window_size, softcap=self.softcap)
         return ops.bf16_linear(o.view(bs, self.hq * self.hd), self.wo)
 
     def decode_from_residual(self, x, pending, norm_weight, eps, cos, sin):
@@ -138,7 +149,7 @@ class LlamaAttention(torch.nn.Module):
         else:
             self.cache.finalize_cache_bylayer_prefill(k, v, self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
         o = self.attn_backend.attn_varlen_func(q, k, v, varlens.prefix_lens, varlens.prefix_lens, varlens.max_len,
-                                               varlens.max_len, causal=True)
+                                               varlens.max_len, causal=True, window_size=self.window_size, softcap=self.softcap)
         return ops.bf16_linear(o.reshape(T, self.hq * self.hd), self.wo)
 
 

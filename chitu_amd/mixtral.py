@@ -9,6 +9,7 @@ expert loop is fused_moe.fused_experts(use_int8_w8a8=True).  Attention, norms an
 """
 
 from dataclasses import dataclass
+from typing import Optional
 
 import torch
 
@@ -33,6 +34,8 @@ class MixtralArgs:
     num_local_experts: int = 8
     num_experts_per_tok: int = 2
     kv_cache_dtype: str = "bf16"  # "fp8": see LlamaArgs.kv_cache_dtype
+    sliding_window: Optional[int] = None  # see LlamaArgs.sliding_window
+    attn_softcap: float = 0.0  # see LlamaArgs.attn_softcap
 
     @property
     def head_dim(self):

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 7  /* 7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 8  /* 8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -524,6 +524,19 @@ int chitu_hip_gqa_prefill(const void* q_bf16, int64_t q_stride_t, int64_t q_stri
                           float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
                           void* stream);
 
+/* chitu_hip_gqa_prefill_window: chitu_hip_gqa_prefill over a sliding window and / or with a soft cap -- window_size = (window_left, 0) and softcap of the same
+ * attn_varlen_func call (chitu/attn_backend.py:39-90, the window rule :67-69; the arithmetic is RefAttnBackend._attention,
+ * :294-392, which FlashAttnBackend forwards to flash_attn, :167-206).  The argument list above with two more before the stream:
+ *   window_left = W >= 0: query position p (inside its own sequence) sees the keys p - W .. p; W = 0: only itself; -1: no window.
+ *   softcap = c > 0: the score is c * tanh(softmax_scale * q.k / c), before the mask and the softmax; 0: off.
+ * window_left < -1 or softcap < 0 (or NaN): CHITU_ERR_BAD_ARG.  (-1, 0) launches chitu_hip_gqa_prefill's own kernel.  A workgroup
+ * starts at the 64-key tile that holds its lowest visible key, so the work per query token is bounded by W + 128 keys. */
+int chitu_hip_gqa_prefill_window(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16,
+                                 int64_t k_stride_t, int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t,
+                                 int64_t v_stride_h, const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen,
+                                 float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                                 int32_t window_left, float softcap, void* stream);
+
 /* chitu_hip_mla_decode (num_splits >= 2) AND the merge + W_UV projection + act_quant of the entry below in ONE launch:
  * AttentionDeepSeekV3.decode_forward's mla_attn_with_kvcache -> einsum("bshc,hdc->bshd") -> act_quant of wo's input
  * (chitu/models/model_deepseek_v3.py:672-699, chitu/attn_backend.py:707-774).  Every split workgroup publishes its partial
@@ -803,6 +816,34 @@ int chitu_hip_gqa_decode_kv_fp8(const void* q_bf16, int64_t q_stride_b, int64_t 
                                 float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads,
                                 int32_t head_dim, int32_t num_splits, void* workspace, int64_t workspace_bytes,
                                 void* stream);
+
+/* ---- Sliding-window and soft-capped GQA / MHA paged decode (csrc/gqa_decode_tile.h, kWin) ----------------------------------
+ * window_size = (window_left, 0) and softcap of attn_with_kvcache (chitu/attn_backend.py:92-164, the window rule :136-138;
+ * FlashAttnBackend forwards both to flash_attn, :208-243; the arithmetic is RefAttnBackend._attention, :294-392).
+ * chitu_hip_gqa_decode's / chitu_hip_gqa_decode_kv_fp8's argument list, contract, workspace and limits with two more arguments
+ * before the stream:
+ *   window_left = W >= 0: the query (position L - 1, L = seqlens[b]) sees the keys w0 = max(0, L - 1 - W) .. L - 1; W = 0: only
+ *     the row appended this step; -1: no window.
+ *   softcap = c > 0: the score is c * tanh(softmax_scale * q.k / c), before the mask and the softmax; 0: off.
+ * window_left < -1 or softcap < 0 (or NaN): CHITU_ERR_BAD_ARG.  (-1, 0) launches the plain entry's own kernel: same bits,
+ * workspace partials included.  With a window the 16-token steps [w0 / 16, ceil(L / 16)) are divided among the splits the way
+ * [0, ceil(L / 16)) is without one, so for w0 % 16 == 0 and page_size 16 the call equals, bit for bit, the plain call on the
+ * table shifted left by w0 / 16 pages with length L - w0.  Rows before w0 are as free as rows past L: whatever they hold (NaN
+ * rows, NaN codes and scales) is never used, and a table entry of a page wholly before the window is never read.
+ *   chitu_hip_gqa_decode_window          bf16 caches.
+ *   chitu_hip_gqa_decode_kv_fp8_window   144-byte fp8 rows; bit-identical to the bf16 entry on the dequantised cache. */
+int chitu_hip_gqa_decode_window(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_h, const void* k_cache,
+                                const void* v_cache, int64_t num_pages, int32_t page_size, int32_t kv_heads,
+                                const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                                float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads,
+                                int32_t head_dim, int32_t num_splits, void* workspace, int64_t workspace_bytes,
+                                int32_t window_left, float softcap, void* stream);
+int chitu_hip_gqa_decode_kv_fp8_window(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_h, const void* k_cache,
+                                       const void* v_cache, int64_t num_pages, int32_t page_size, int32_t kv_heads,
+                                       const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                                       float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads,
+                                       int32_t head_dim, int32_t num_splits, void* workspace, int64_t workspace_bytes,
+                                       int32_t window_left, float softcap, void* stream);
 
 /* ---- token sampling (the step after the path) -----------------------------------
  * Replaces NormalExecutor.update_response's device work (chitu/executor.py:82-112) and

@@ -9,6 +9,12 @@ both arms alike.  Before any time is taken, the fp8 arm's output is checked bit 
 DEQUANTISED fp8 cache at the same split count; a shape that fails the check reports no times.  Per arm: median with min .. max
 over the replays, K + V bytes read, TB/s; then fp8 / bf16.  One launch sequence re-reads the same caches 20 times: at the
 smallest shapes (bs 1, ctx 1024: 4 MB of bf16 rows) they stay in the last-level cache, and the figure is not an HBM rate.
+
+  --window W: the same launches with window_size = (W, 0) (chitu_hip_gqa_decode_window / _kv_fp8_window) join the alternation as
+two more arms per shape, after the windowed fp8 output is checked bit for bit against the windowed bf16 kernel on the dequantised
+cache and the windowed bf16 output against the unwindowed kernel on the last W + 1 keys alone (attention bar, 1e-2 of the peak).
+A windowed launch at context L reads the bytes the unwindowed launch reads at context W + 1: when the sweep also holds
+ctx = W + 1, every windowed row reports its time over that row's unwindowed time of the same batch size and process.
 """
 import argparse
 import json
@@ -28,6 +34,7 @@ ap.add_argument("--ctx", type=int, nargs="*", default=[1024, 4096, 8192, 32768])
 ap.add_argument("--repeats", type=int, default=15)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--per-graph", type=int, default=20, help="launch sequences per captured graph")
+ap.add_argument("--window", type=int, default=None, help="also time the launches with window_size=(W, 0)")
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 
@@ -93,15 +100,28 @@ def main():
             new_v = torch.randn(bs, HKV, D, device="cuda", generator=g).to(torch.bfloat16)
             old = lens - 1
 
-            def decode(kc, vc):
-                return be.attn_with_kvcache(q, kc, vc, cache_seqlens=lens, block_table=table)
+            def decode(kc, vc, window=-1):
+                return be.attn_with_kvcache(q, kc, vc, cache_seqlens=lens, block_table=table, window_size=(window, 0))
 
             dk, dv = ops.gqa_kv_dequant_fp8(k8), ops.gqa_kv_dequant_fp8(v8)
             same = torch.equal(decode(k8, v8).view(torch.int16), decode(dk, dv).view(torch.int16))
+            W = a.window
+            if W is not None:
+                # the window's keys alone, as a sequence of its own: the last pages of every table row, the length cut to match
+                w0 = max(0, ctx - 1 - W)
+                cut = w0 // PAGE
+                alone = be.attn_with_kvcache(q, dk, dv, cache_seqlens=lens - w0, block_table=table[:, cut:].contiguous()) if w0 % PAGE == 0 else None
+                win = decode(dk, dv, W)
+                same_w = torch.equal(decode(k8, v8, W).view(torch.int16), win.view(torch.int16))
+                if alone is not None:
+                    same_w = same_w and float((win.float() - alone.float()).abs().max() / alone.float().abs().max()) < 1e-2
+                same = same and same_w
             del dk, dv
             row = {"bs": bs, "ctx": ctx, "splits": gqa_num_splits(bs, HKV, pages_per, PAGE),  # what decode() above was given
                    "kv_MB": {"bf16": round(2 * bs * ctx * ROW16 / 1e6, 2), "fp8": round(2 * bs * ctx * ROW8 / 1e6, 2)},
                    "fp8_equals_bf16_on_dequantised_cache": bool(same)}
+            if W is not None:
+                row.update(window=W, window_splits=gqa_num_splits(bs, HKV, pages_per, PAGE, W), window_keys=min(ctx, W + 1))
             if not same:  # no time is reported for a kernel that computes something else
                 print(json.dumps(row), flush=True)
                 rows.append(row)
@@ -113,6 +133,9 @@ def main():
                       "bf16_append": capture(lambda: (ops.append_to_paged_kv_cache(k16, table, new_k, old),
                                                       ops.append_to_paged_kv_cache(v16, table, new_v, old)), per),
                       "fp8_append": capture(lambda: ops.append_gqa_kv_fp8(k8, v8, table, new_k, new_v, old), per)}
+            if W is not None:
+                graphs["bf16_decode_window"] = capture(lambda: decode(k16, v16, W), per)
+                graphs["fp8_decode_window"] = capture(lambda: decode(k8, v8, W), per)
             us = alternate(graphs, per)
             row.update({k: stats(v) for k, v in us.items()})
             for fmt, nbytes in (("bf16", 2 * bs * ctx * ROW16), ("fp8", 2 * bs * ctx * ROW8)):
@@ -121,15 +144,29 @@ def main():
             # a difference counts when it exceeds the bf16 arm's own min .. max spread
             row["difference_exceeds_bf16_spread"] = bool(
                 abs(row["bf16_decode"]["median_us"] - row["fp8_decode"]["median_us"]) > row["bf16_decode"]["max_us"] - row["bf16_decode"]["min_us"])
+            if W is not None:
+                for fmt in ("bf16", "fp8"):
+                    row[f"{fmt}_window_over_unwindowed_same_ctx"] = round(row[fmt + "_decode_window"]["median_us"] / row[fmt + "_decode"]["median_us"], 4)
             print(json.dumps(row), flush=True)
             rows.append(row)
             del graphs, k16, v16, k8, v8
             torch.cuda.empty_cache()
+    if a.window is not None:
+        # windowed at ctx against unwindowed at ctx = W + 1 (the same bytes), same batch size, same process
+        for row in rows:
+            base = [r for r in rows if r["bs"] == row["bs"] and r["ctx"] == a.window + 1 and "bf16_decode" in r]
+            if not base or "bf16_decode_window" not in row:
+                continue
+            for fmt in ("bf16", "fp8"):
+                b, w = base[0][fmt + "_decode"], row[fmt + "_decode_window"]
+                row[f"{fmt}_window_over_unwindowed_at_window_ctx"] = round(w["median_us"] / b["median_us"], 4)
+                row[f"{fmt}_window_difference_exceeds_spread"] = bool(abs(w["median_us"] - b["median_us"]) > b["max_us"] - b["min_us"])
+            print(json.dumps({k: v for k, v in row.items() if k in ("bs", "ctx", "splits", "window_splits") or "window_" in k}), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump({"tool": "tools/gqa_ctx_sweep.py", "device": torch.cuda.get_device_name(0), "heads": [HQ, HKV], "page": PAGE,
-                       "launch_sequences_per_graph": a.per_graph, "warmup_replays": a.warmup, "sweep": rows}, f, indent=1)
+                       "launch_sequences_per_graph": a.per_graph, "warmup_replays": a.warmup, "window": a.window, "sweep": rows}, f, indent=1)
             f.write("\n")
 
 
