@@ -30,6 +30,7 @@ def is_fp8_gqa_cache(cache) -> bool:
     return cache.dtype == torch.uint8 and cache.dim() == 4 and cache.shape[-1] == GQA_KV_FP8_ROW
 
 
+GQA_MULTI_MAX_Q = 8  # query tokens per sequence of chitu_hip_gqa_decode_multi (csrc/gqa_decode_multi.hip: kGqaMultiMaxQ)
 # Upper bound of the KV splits of the GQA decode launch (graph-static: sized from the page table's width, not from the
 # lengths).  32 by the sweep of round 4 (Llama-3-8B bs 1, ctx 1024: 64 -> 3.064, 32 -> 3.041, 16 -> 3.077, 8 -> 3.175 ms/step;
 # from bs 4 on the CU-count term decides; profiles/r04_gqa_split_sweep.txt); CHITU_GQA_MAX_SPLITS overrides it for sweeps.
@@ -484,11 +485,23 @@ class HipAttnBackend(AttnBackend):
         semantics, :136-138 and RefAttnBackend._attention): the query sees the last W + 1 keys, the appended one included, and
         the score is softcap * tanh(scale * q.k / softcap).  chitu_hip_gqa_decode_window / _kv_fp8_window, taken only when a
         window or a cap is set; they read only the pages the window overlaps.  A right window on a non-causal call raises.
+
+        q [bs, T, Hq, 128] with 1 < T <= 8 (the contract's seqlen > 1; a speculative verify step): k / v [bs, T, Hkv, 128] are
+        written at cache_seqlens[b] .. + T - 1, then query t attends to the keys k <= cache_seqlens[b] + t (within the window:
+        k >= cache_seqlens[b] + t - W) -- the causal mask aligned to the bottom right.  Needs causal=True or a window whose right
+        side is 0 (anything else: NotImplementedError).  chitu_hip_gqa_decode_multi / _kv_fp8 (csrc/gqa_decode_multi.hip):
+        16 // (Hq // Hkv) query tokens share one walk over the pages.  Returns [bs, T, Hq, 128].
         """
         assert block_table is not None, "HipAttnBackend.attn_with_kvcache is the paged path"
         assert cache_leftpad is None, "cache_leftpad is not implemented"
         window_left, softcap = window_and_cap(window_size, softcap, causal)
-        assert q.dim() == 4 and q.shape[1] == 1, "decode: one query token per sequence"
+        assert q.dim() == 4 and 1 <= q.shape[1] <= GQA_MULTI_MAX_Q, f"decode: 1 .. {GQA_MULTI_MAX_Q} query tokens per sequence"
+        if q.shape[1] > 1:
+            if not causal and int(window_size[1]) != 0:
+                raise NotImplementedError(f"{q.shape[1]} query tokens with causal=False and window_size={tuple(window_size)}: only the "
+                                          "causal mask (causal=True, or a window whose right side is 0) is implemented")
+            return self._attn_with_kvcache_multi(q, k_cache, v_cache, k, v, cache_seqlens, block_table, window_left, softcap,
+                                                 softmax_scale, num_splits)
         require_cuda(q, k_cache, v_cache, cache_seqlens, block_table)
         fp8_kv = is_fp8_gqa_cache(k_cache)
         if fp8_kv:
@@ -532,3 +545,51 @@ class HipAttnBackend(AttnBackend):
             name,
         )
         return out.view(bs, 1, Hq, D)
+
+    def _attn_with_kvcache_multi(self, q, k_cache, v_cache, k, v, cache_seqlens, block_table, window_left, softcap, softmax_scale,
+                                 num_splits):
+        """attn_with_kvcache for q [bs, T, Hq, 128], T > 1.  The append runs the single-token append kernels on the bs * T
+        expanded rows (row (b, t): table row b, position cache_seqlens[b] + t)."""
+        require_cuda(q, k_cache, v_cache, cache_seqlens, block_table)
+        fp8_kv = is_fp8_gqa_cache(k_cache)
+        if fp8_kv:
+            assert q.dtype == torch.bfloat16 and is_fp8_gqa_cache(v_cache) and q.shape[-1] == 128
+        else:
+            assert q.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16
+        assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape
+        assert cache_seqlens.dtype == torch.int32 and block_table.dtype == torch.int32 and block_table.stride(1) == 1
+        bs, T, Hq, D = q.shape
+        Hkv = k_cache.shape[2]
+        if softmax_scale is None:
+            softmax_scale = D ** -0.5
+        seqlens = cache_seqlens
+        if k is not None:
+            assert v is not None and k.shape[:2] == (bs, T) and v.shape[:2] == (bs, T)
+            rows_table = block_table.repeat_interleave(T, dim=0).contiguous()
+            rows_lens = (cache_seqlens.view(bs, 1) + torch.arange(T, dtype=torch.int32, device=q.device)).view(bs * T)
+            kr, vr = k.reshape(bs * T, Hkv, D), v.reshape(bs * T, Hkv, D)
+            if fp8_kv:
+                append_gqa_kv_fp8(k_cache, v_cache, rows_table, kr, vr, rows_lens)
+            else:
+                append_to_paged_kv_cache(k_cache, rows_table, kr.contiguous(), rows_lens)
+                append_to_paged_kv_cache(v_cache, rows_table, vr.contiguous(), rows_lens)
+            seqlens = cache_seqlens + T
+        if not (q.stride(-1) == 1 and all(q.stride(i) % 8 == 0 for i in range(3)) and q.data_ptr() % 16 == 0):
+            q = q.contiguous()
+        if num_splits is None:
+            tiles = -(-T // (16 // (Hq // Hkv)))  # workgroups per (sequence, kv head): 16 // G query tokens share one
+            num_splits = gqa_num_splits(bs * tiles, Hkv, int(block_table.shape[1]), int(k_cache.shape[1]), window_left)
+        out = torch.empty(bs, T, Hq, D, dtype=torch.bfloat16, device=q.device)
+        need = bs * T * Hq * num_splits * (D + 1) * 4 if num_splits > 1 else 1
+        ws = workspace.get(need, q.device, "gqa")
+        name = "gqa_decode_multi_kv_fp8" if fp8_kv else "gqa_decode_multi"
+        check(
+            getattr(_lib.lib(), "chitu_hip_" + name)(
+                ptr(q), i64(q.stride(0)), i64(q.stride(1)), i64(q.stride(2)), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]),
+                i32(k_cache.shape[1]), i32(Hkv), ptr(block_table), i32(block_table.stride(0)), ptr(seqlens),
+                f32(softmax_scale), ptr(out), i32(bs), i32(T), i32(Hq), i32(D), i32(num_splits), ptr(ws), i64(ws.numel()),
+                i32(window_left), f32(softcap), stream_ptr(),
+            ),
+            name,
+        )
+        return out

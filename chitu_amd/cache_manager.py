@@ -19,6 +19,7 @@ logger = getLogger(__name__)
 _BLOCK_SIZE = 512
 _MAX_SEQ_LEN = 2048
 _STAGE_RING = 4
+MAX_DECODE_Q = 8  # query tokens per request of a multi-token decode step (attn_backend.GQA_MULTI_MAX_Q)
 
 
 MLA_KV_CACHE_DTYPES = ("bf16", "fp8")
@@ -108,6 +109,8 @@ class PagedKVCacheManager:
         self._stage_events = {"lens": [None] * _STAGE_RING, "table": [None] * _STAGE_RING}
         self._stage_next = {"lens": 0, "table": 0}
         self._table_rows = None  # request ids whose rows the device table currently holds, in order (None = stale)
+        self._multi_dev = self._multi_table_dev = None  # the multi-token step's buffers (_multi_buffers)
+        self._multi_shape = (0, 1)
         self.free_blocks = deque(range(self.num_blocks))
         if self.kv_shape_per_sample is not None:
             self.paged_kv_cache = torch.zeros(
@@ -247,6 +250,89 @@ class PagedKVCacheManager:
             self._stage_done("table", slot)
             self._table_rows = list(req_ids)
         self.gpu_block_table = self.gpu_block_table_buffer[:n]
+
+    # ---- multi-token decode steps (a speculative verify step: T query tokens per sequence, attn_with_kvcache's seqlen > 1)
+    def _multi_buffers(self):
+        """Persistent buffers of the multi-token step, made at its first use: a captured step replays on their addresses.
+        Sized for MAX_DECODE_Q tokens per request, so one allocation serves every T."""
+        if self._multi_dev is None:
+            n, rows = self._lens_dev.shape[1], self._lens_dev.shape[1] * MAX_DECODE_Q
+            # [row lengths (rows) | lengths incl. the T new tokens (n)] in one allocation: one copy refreshes both
+            self._multi_dev = torch.zeros(rows + n, dtype=torch.int32, device=self.device)
+            self._multi_table_dev = torch.zeros((rows, self.max_blocks_per_req), dtype=torch.int32, device=self.device)
+            self._multi_host = torch.zeros(_STAGE_RING, rows + n, dtype=torch.int32, pin_memory=self._pinned)
+            self._multi_host_table = torch.zeros((_STAGE_RING, rows, self.max_blocks_per_req), dtype=torch.int32,
+                                                 pin_memory=self._pinned)
+            self._stage_events.update(multi=[None] * _STAGE_RING, multi_table=[None] * _STAGE_RING)
+            self._stage_next.update(multi=0, multi_table=0)
+        return self._multi_dev
+
+    def prepare_block_table_for_decode_multi(self, req_ids, T):
+        """Make room for the T tokens this step appends to every request and stage what the step reads, in persistent
+        buffers of its own (the single-token step's buffers are not touched):
+          get_gpu_multi_row_lens()      [n * T] the old length + t of expanded row (b, t): its RoPE and append position
+          get_gpu_multi_seq_lens_incl() [n]     the old length + T: the keys the attention sees
+          get_gpu_multi_block_table()   [n * T, max_blocks] request b's table in each of its T rows (the append kernels take one
+                                        table row per appended row; the attention reads every T-th row)
+        Pages beyond ceil(len / block_size) that a step takes and finalize_cache_multi_decode does not keep go back to the
+        free list there."""
+        assert 1 <= T <= MAX_DECODE_Q
+        n = len(req_ids)
+        assert n * MAX_DECODE_Q <= self._multi_buffers().numel()
+        for req_id in req_ids:  # every request's capacity first: a refused step has taken no page
+            if self.seq_lens[req_id] + T > self.max_blocks_per_req * self.block_size:
+                raise Exception(f"request {req_id!r}: {self.seq_lens[req_id]} + {T} tokens do not fit its block table")
+        for req_id in req_ids:
+            while len(self.block_table[req_id]) * self.block_size < self.seq_lens[req_id] + T:
+                self.block_table[req_id].append(self.get_free_block())
+                self._table_rows = None  # the single-token step's device table no longer shows this request's pages
+        lens = [self.seq_lens[r] for r in req_ids]
+        slot = self._stage_slot("multi")
+        h = self._multi_host[slot].numpy()
+        rows = n * T
+        for b, L0 in enumerate(lens):
+            h[b * T : (b + 1) * T] = range(L0, L0 + T)
+        h[rows : rows + n] = [L0 + T for L0 in lens]
+        self._multi_dev[: rows + n].copy_(self._multi_host[slot][: rows + n], non_blocking=True)
+        self._stage_done("multi", slot)
+        slot = self._stage_slot("multi_table")
+        ht = self._multi_host_table[slot].numpy()
+        ht[:rows] = 0
+        for b, req_id in enumerate(req_ids):
+            ids = self.block_table[req_id]
+            ht[b * T : (b + 1) * T, : len(ids)] = ids
+        self._multi_table_dev[:rows].copy_(self._multi_host_table[slot, :rows], non_blocking=True)
+        self._stage_done("multi_table", slot)
+        self._multi_shape = (n, T)
+
+    def get_gpu_multi_row_lens(self):
+        n, T = self._multi_shape
+        return self._multi_dev[: n * T]
+
+    def get_gpu_multi_seq_lens_incl(self):
+        n, T = self._multi_shape
+        return self._multi_dev[n * T : n * T + n]
+
+    def get_gpu_multi_block_table(self):
+        n, T = self._multi_shape
+        return self._multi_table_dev[: n * T]
+
+    def finalize_cache_multi_decode(self, req_ids, n_accepted):
+        """After a multi-token step of T tokens: request b keeps the first n_accepted[b] of them (1 <= n_accepted[b] <= T).  Its
+        length advances by that, and the pages beyond ceil(length / block_size) go back to the free list -- the single-token
+        methods' invariant.  The rejected rows stay behind the length as garbage: no kernel uses bytes past a length."""
+        n, T = self._multi_shape
+        assert len(req_ids) == n and len(n_accepted) == n
+        for req_id, acc in zip(req_ids, n_accepted):
+            acc = int(acc)
+            assert 1 <= acc <= T, f"request {req_id!r}: {acc} accepted tokens of a step of {T}"
+            self.seq_lens[req_id] += acc
+            keep = (self.seq_lens[req_id] + self.block_size - 1) // self.block_size
+            while len(self.block_table[req_id]) > keep:
+                self.free_blocks.append(self.block_table[req_id].pop())
+                self._table_rows = None
+        self.curr_varlens = None
+        self.curr_req_ids = None
 
     def finalize_cache_single_decode(self, req_ids):
         for req_id in req_ids:

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 
 from . import graphs, ops
 from . import tensor_parallel as tp
-from .attn_backend import HipAttnBackend
+from .attn_backend import GQA_MULTI_MAX_Q, HipAttnBackend
 from .cache_manager import PagedKVCacheManager, gqa_kv_layout
 
 
@@ -95,25 +95,38 @@ class LlamaAttention(torch.nn.Module):
         self.wqkv = _param((self.hq + 2 * self.hkv) * self.hd, args.dim, device=device)
         self.wo = _param(args.dim, self.hq * self.hd, device=device)
 
-    def decode_forward_paged(self, x, cos, sin):
+    def decode_forward_paged(self, x, cos, sin, q_len=1):
         """x = attn_norm(h) bf16 [bs, dim] -> wo(attention) before the all-reduce (model.py:167-198)."""
-        return self.decode_from_qkv(ops.bf16_linear(x, self.wqkv), cos, sin)
+        return self.decode_from_qkv(ops.bf16_linear(x, self.wqkv), cos, sin, q_len)
 
-    def decode_from_qkv(self, qkv, cos, sin):
+    def _row_tables(self, q_len):
+        """(block table, old length) per row of the step: one row per sequence, or -- a multi-token step, q_len > 1 -- one per
+        (sequence, token) in that order (PagedKVCacheManager.prepare_block_table_for_decode_multi)."""
+        if q_len > 1:
+            return self.cache.get_gpu_multi_block_table(), self.cache.get_gpu_multi_row_lens()
+        return self.cache.get_gpu_block_table(), self.cache.get_gpu_seq_lens_excl_this_decode()
+
+    def decode_from_qkv(self, qkv, cos, sin, q_len=1):
         """The merged projection's output [bs, (hq + 2 hkv) * hd] -> wo(attention) before the all-reduce."""
         bs = qkv.shape[0]
         qkv = qkv.view(bs, self.hq + 2 * self.hkv, self.hd)
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
         # RoPE(q, k) + append of k and v to their pages: one launch (fp8 cache: with quantising stores)
         post = ops.gqa_qkv_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_post
-        q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, self.cache.get_gpu_block_table(),
-                 self.cache.get_gpu_seq_lens_excl_this_decode(), rotary_type=self.rotary_type)
-        return self.decode_from_q(q)
+        q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), rotary_type=self.rotary_type)
+        return self.decode_from_q(q, q_len)
 
-    def decode_from_q(self, q):
-        """Rotated q heads [bs, hq, hd] (this token's k and v already in their pages) -> wo(attention)."""
+    def decode_from_q(self, q, q_len=1):
+        """Rotated q heads [bs, hq, hd] (this token's k and v already in their pages) -> wo(attention).  q_len > 1: the rows are
+        q_len consecutive tokens of bs / q_len sequences, all their k and v in the pages: one multi-token attention call."""
         bs = q.shape[0]
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
+        if q_len > 1:
+            o = self.attn_backend.attn_with_kvcache(
+                q.view(bs // q_len, q_len, self.hq, self.hd), k_cache, v_cache, None, None,
+                cache_seqlens=self.cache.get_gpu_multi_seq_lens_incl(), block_table=self.cache.get_gpu_multi_block_table()[::q_len],
+                causal=True, window_size=self.window_size, softcap=self.softcap)
+            return ops.bf16_linear(o.view(bs, self.hq * self.hd), self.wo)
         table = self.cache.get_gpu_block_table()
         o = self.attn_backend.attn_with_kvcache(
             q.unsqueeze(1), k_cache, v_cache, None, None,
@@ -121,18 +134,17 @@ class LlamaAttention(torch.nn.Module):
             window_size=self.window_size, softcap=self.softcap)
         return ops.bf16_linear(o.view(bs, self.hq * self.hd), self.wo)
 
-    def decode_from_residual(self, x, pending, norm_weight, eps, cos, sin):
+    def decode_from_residual(self, x, pending, norm_weight, eps, cos, sin, q_len=1):
         """Small decode batches: residual add + attn_norm + wqkv projection [+ RoPE and the K / V page append when the
         rotary pairs are interleaved] in ONE launch.  Returns (x + pending, wo(attention) before the all-reduce).  The fused
         epilogue writes bf16 page rows: an fp8 cache takes the two-launch form of "hf-llama"."""
         if self.rotary_type == "llama" and not self.fp8_kv:
             k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
             x, qkv = ops.bf16_linear_add_norm_qkv_post(
-                x, pending, norm_weight, eps, self.wqkv, self.hq, self.hkv, cos, sin, k_cache, v_cache,
-                self.cache.get_gpu_block_table(), self.cache.get_gpu_seq_lens_excl_this_decode())
-            return x, self.decode_from_q(qkv[:, : self.hq])
+                x, pending, norm_weight, eps, self.wqkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len))
+            return x, self.decode_from_q(qkv[:, : self.hq], q_len)
         x, qkv = ops.bf16_linear_add_norm(x, pending, norm_weight, eps, self.wqkv)
-        return x, self.decode_from_qkv(qkv, cos, sin)
+        return x, self.decode_from_qkv(qkv, cos, sin, q_len)
 
     def prefill_forward(self, x, cos, sin, varlens):
         """models/model.py:104-132: projections on all T prompt tokens, RoPE, page writes by the cache
@@ -176,17 +188,17 @@ class LlamaBlock(torch.nn.Module):
         self.ffn_norm = _param(args.dim, device=device)
         self.eps = args.norm_eps
 
-    def forward(self, x, pending, cos, sin, varlens=None):
+    def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
         """(x, pending) -> (x', pending'): residual adds folded into the RMSNorm that consumes them;
-        varlens given = prefill."""
+        varlens given = prefill; q_len > 1: the rows are q_len tokens per sequence (LlamaDecoder.decode_multi)."""
         if varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0]):
             # small decode batches: the add + norm run as the prologue of the projection that consumes them
-            x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin)
+            x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin, q_len)
             a = tp.defer_all_reduce(a)
         else:
             x, hn = tp.add_norm(x, pending, self.attn_norm, self.eps)[:2]
             if varlens is None:
-                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin))
+                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin, q_len))
             else:
                 a = tp.defer_all_reduce(self.attn.prefill_forward(hn, cos, sin, varlens))
         return self.ffn_part(x, a, varlens)
@@ -291,15 +303,18 @@ class LlamaDecoder(torch.nn.Module):
             tp.check_comm()
         return tokens_out
 
-    def decode_eager(self, tokens):
-        # embedding rows of this rank's vocabulary slice + every sequence's rotary row: one launch
+    def decode_eager(self, tokens, q_len=1):
+        """tokens [rows] int64.  q_len > 1: rows = q_len consecutive tokens of each sequence, positions and page rows from the
+        cache manager's multi-token buffers."""
+        # embedding rows of this rank's vocabulary slice + every row's rotary row: one launch
+        positions = self.cache.get_gpu_multi_row_lens() if q_len > 1 else self.cache.get_gpu_seq_lens_excl_this_decode()
         h, cos, sin = ops.embed_rope_gather(tokens, self.embed_weight, self.vocab_start if self.vocab_local != self.args.vocab_size else 0,
-                                            self.cache.get_gpu_seq_lens_excl_this_decode(), self.cos_table, self.sin_table)
+                                            positions, self.cos_table, self.sin_table)
         if self.vocab_local != self.args.vocab_size:
             h = tp.all_reduce(h)
         pending = None
         for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin)
+            h, pending = layer(h, pending, cos, sin, q_len=q_len)
         h = tp.add_norm(h, pending, self.norm, self.args.norm_eps)[1]
         return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
 
@@ -325,6 +340,98 @@ class LlamaDecoder(torch.nn.Module):
             self.graphs[key] = g
         self.graphs[key].replay()
         return self.static_out[bs]
+
+    @torch.inference_mode()
+    def decode_multi(self, tokens, use_graph=True):
+        """One step over T = tokens.shape[1] tokens per sequence (1 < T <= 8): tokens [bs, T] int64 are appended at each
+        sequence's length .. + T - 1 and token t attends to everything up to itself -- the verify step of speculative decoding.
+        Returns fp32 logits [bs, T, vocab]: row (b, t) predicts the token after tokens[b, t].  The caller has run
+        cache.prepare_block_table_for_decode_multi(req_ids, T) and settles the lengths with finalize_cache_multi_decode.
+
+        The stack runs on bs * T rows (embedding, norms, GEMMs and the RoPE + append launch take per-row positions; the fused
+        small-batch launches apply by their row limits on bs * T); only the attention call knows T.  Graph replay as in decode(),
+        keyed (bs, T, mode), on static buffers of its own."""
+        tp.check_comm()
+        assert tokens.dim() == 2 and tokens.dtype == torch.int64
+        bs, T = tokens.shape
+        if T == 1:
+            raise ValueError("decode_multi is the multi-token step (T > 1); decode() is the single-token one")
+        flat = tokens.reshape(bs * T)
+        if not use_graph or tp.xgmi_split_phase():
+            return self.decode_eager(flat, T).view(bs, T, -1)
+        mode = graphs.graph_mode(use_graph)
+        key, skey = (bs, T, mode), (bs, T)
+        if skey not in self.static_tokens:
+            self.static_tokens[skey] = flat.clone()
+        else:
+            self.static_tokens[skey].copy_(flat)
+        if key not in self.graphs:
+            g, self.graph_pool, self.static_out[skey] = graphs.capture_verified(
+                lambda: self.decode_eager(self.static_tokens[skey], T), self.static_out.get(skey), mode, self.graph_pool,
+                what=f"{type(self).__name__} multi-token decode step bs={bs} T={T}")
+            self.graphs[key] = g
+        self.graphs[key].replay()
+        return self.static_out[skey].view(bs, T, -1)
+
+    @torch.inference_mode()
+    def generate_speculative(self, prompts, max_new_tokens, drafter, draft_len, req_ids=None, use_graph=True, temperatures=None,
+                             top_ks=None, top_ps=None, frequency_penalties=None, generator=None):
+        """Greedy generation with draft-and-verify: the tokens plain greedy generate() picks, in fewer steps when the drafter is
+        right.  Each round, drafter.propose(history, draft_len) names draft_len tokens per request (history = prompt + tokens
+        so far), ONE decode_multi step runs over [last token | drafts], the longest prefix with draft[i] == argmax(logits[i]) is
+        accepted, the argmax at the first mismatch (or after the last draft) is emitted as the bonus token, and the cache
+        keeps accepted + 1 rows.  A request leaves the batch when it has max_new_tokens.  Returns [n_req, max_new_tokens] int64
+        and frees the requests' pages; self.speculative_stats = {"steps": verify steps run, "accepted": drafts accepted,
+        "drafted": drafts proposed}.  Greedy only: any sampling argument raises.  The drafter runs on the host: the accepted
+        counts have to reach the host for the page accounting anyway (one small copy per round).  Every request needs room
+        for draft_len tokens beyond prompt + max_new_tokens in its block table."""
+        from . import sampling
+
+        if any(a is not None for a in (temperatures, top_ks, top_ps, frequency_penalties, generator)):
+            raise NotImplementedError("generate_speculative is greedy: the acceptance rule draft == argmax has no sampling form here")
+        if not 1 <= draft_len <= GQA_MULTI_MAX_Q - 1:
+            raise ValueError(f"draft_len={draft_len}: a verify step holds the last token and 1 .. {GQA_MULTI_MAX_Q - 1} drafts")
+        n_req = len(prompts)
+        req_ids = [f"gen{i}" for i in range(n_req)] if req_ids is None else list(req_ids)
+        T = draft_len + 1
+        first = sampling.argmax(self.prefill(prompts, req_ids)).tolist()
+        out = [[t] for t in first]
+        stats = {"steps": 0, "accepted": 0, "drafted": 0}
+        live = list(range(n_req))
+        if max_new_tokens <= 1:
+            live = []
+            for r in req_ids:
+                self.cache.finalize_cache_all_decode(r)
+        while live:
+            drafts = []
+            for i in live:
+                d = [int(t) for t in drafter.propose(list(prompts[i]) + out[i], draft_len)]
+                assert len(d) == draft_len, f"drafter proposed {len(d)} tokens, not draft_len={draft_len}"
+                drafts.append(d)
+            ids = [req_ids[i] for i in live]
+            self.cache.prepare_block_table_for_decode_multi(ids, T)
+            step = torch.tensor([[out[i][-1]] + d for i, d in zip(live, drafts)], dtype=torch.int64, device=self.device)
+            logits = self.decode_multi(step, use_graph=use_graph)
+            best = sampling.argmax(logits.view(len(live) * T, -1)).view(len(live), T).tolist()
+            kept = []
+            for i, d, a in zip(live, drafts, best):
+                n_ok = 0
+                while n_ok < draft_len and d[n_ok] == a[n_ok]:
+                    n_ok += 1
+                out[i].extend(d[:n_ok] + [a[n_ok]])
+                kept.append(n_ok + 1)
+                stats["accepted"] += n_ok
+                stats["drafted"] += draft_len
+            stats["steps"] += 1
+            self.cache.finalize_cache_multi_decode(ids, kept)
+            for i in [i for i in live if len(out[i]) >= max_new_tokens]:
+                self.cache.finalize_cache_all_decode(req_ids[i])
+                live.remove(i)
+        self.speculative_stats = stats
+        if tp.xgmi_comm() is not None:
+            torch.cuda.current_stream().synchronize()
+            tp.check_comm()
+        return torch.tensor([o[:max_new_tokens] for o in out], dtype=torch.int64, device=self.device)
 
 
 @torch.no_grad()

@@ -83,16 +83,16 @@ class MixtralBlock(torch.nn.Module):
         self.ffn_norm = _param(args.dim, device=device)
         self.eps = args.norm_eps
 
-    def forward(self, x, pending, cos, sin, varlens=None):
+    def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
         if FUSE and varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0], two_terms_ok=self.attn.rotary_type != "llama"):
             # small decode batches: residual add + attn_norm run as the prologue of the qkv projection (round 6: the Llama
             # blocks' fusion, bit-identical, one launch less per layer)
-            x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin)
+            x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin, q_len)
             a = tp.defer_all_reduce(a)
         else:
             x, hn = tp.add_norm(x, pending, self.attn_norm, self.eps)[:2]
             if varlens is None:
-                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin))
+                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin, q_len))
             else:
                 a = tp.defer_all_reduce(self.attn.prefill_forward(hn, cos, sin, varlens))
         # ffn_norm with the experts' per-token int8 quantisation of its output in the same launch (round 6: quant_act's arithmetic

@@ -30,6 +30,7 @@ __all__ = [
     "top_k_top_p_min_p_sampling_from_probs_torch",
     "sample_tokens",
     "DeviceSampler",
+    "NgramDrafter",
 ]
 
 
@@ -203,3 +204,30 @@ class DeviceSampler:
             self.history[:, t] = tok.to(torch.int32)
         self.n_generated = t + 1
         return tok
+
+
+class NgramDrafter:
+    """Prompt-lookup drafts for LlamaDecoder.generate_speculative: propose(history, k) returns the k tokens that followed the
+    latest EARLIER occurrence of the history's last n tokens (an occurrence that ends before the history's end, so it has at
+    least one token behind it); where that continuation runs into the end of the history it goes on repeating the last token it
+    gave.  No earlier occurrence (or fewer than n tokens of history): the last token k times.  Runs on the host over Python ints
+    -- the verify step's accepted counts go to the host every round anyway."""
+
+    def __init__(self, n: int = 2):
+        if n < 1:
+            raise ValueError(f"NgramDrafter(n={n}): the lookup key has at least one token")
+        self.n = n
+
+    def propose(self, history: Sequence[int], k: int) -> List[int]:
+        h = [int(t) for t in history]
+        assert h and k >= 0
+        n = self.n
+        out: List[int] = []
+        if len(h) > n:
+            key = h[-n:]
+            for start in range(len(h) - n - 1, -1, -1):  # latest first; start + n <= len(h) - 1: one token follows at least
+                if h[start : start + n] == key:
+                    out = h[start + n : start + n + k]
+                    break
+        fill = out[-1] if out else h[-1]
+        return out + [fill] * (k - len(out))

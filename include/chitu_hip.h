@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 8  /* 8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 9  /* 9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -844,6 +844,40 @@ int chitu_hip_gqa_decode_kv_fp8_window(const void* q_bf16, int64_t q_stride_b, i
                                        float softmax_scale, void* out_bf16, int32_t batch, int32_t q_heads,
                                        int32_t head_dim, int32_t num_splits, void* workspace, int64_t workspace_bytes,
                                        int32_t window_left, float softcap, void* stream);
+
+/* ---- Multi-token GQA / MHA paged decode (csrc/gqa_decode_multi.hip) -------------------------------------------------------
+ * The `seqlen > 1` half of attn_with_kvcache (chitu/attn_backend.py:92-164: q (batch, seqlen, nheads, headdim), k / v of
+ * seqlen_new rows appended at cache_seqlens, the causal mask aligned to the bottom right, the window formula for seqlen_q > 1;
+ * the arithmetic is RefAttnBackend._attention, :294-392) for q_len = T in 1 .. 8: the verify step of speculative decoding.
+ * chitu_hip_gqa_decode_window's argument list, contract, workspace layout and limits with q_stride_t after q_stride_b and q_len
+ * after batch:
+ *   q [batch, T, q_heads, 128] bf16 (element strides, multiples of 8); seqlens[b] = L counts ALL keys of sequence b, the T rows
+ *   appended this step included; out [batch, T, q_heads, 128] bf16 contiguous.
+ *   Query token t sits at position L - T + t and sees key k iff k <= L - T + t and, with window_left = W >= 0,
+ *   k >= L - T + t - W: query (b, t) is chitu_hip_gqa_decode_window on a row of length L - T + t + 1 over the same table.  A query
+ *   with no visible key (L - T + t < 0) gives zeros.  softcap as in chitu_hip_gqa_decode_window; (-1, 0.0) are neutral and launch
+ *   the kernel without the window / cap code.
+ *   16 / (q_heads / kv_heads) query tokens share one wave's K / V walk (the q heads of a group and those tokens fill the 16 MFMA
+ *   columns), so the pages are read ceil(T / that) times instead of T times.
+ *   workspace >= batch*T*q_heads*num_splits*129*4 bytes when num_splits > 1: one row of partials per (b, t, h).
+ *   q_len outside 1 .. 8: CHITU_ERR_BAD_ARG.  At q_len == 1 the output and the workspace are bit-identical to
+ *   chitu_hip_gqa_decode / _window (and _kv_fp8 / _kv_fp8_window) at the same num_splits; at q_len > 1 they are NOT the bits of
+ *   batch * T single-token rows (the wave-wide rescale vote sees the other tokens' columns).
+ *   chitu_hip_gqa_decode_multi          bf16 caches.
+ *   chitu_hip_gqa_decode_multi_kv_fp8   144-byte fp8 rows; bit-identical to the bf16 entry on the dequantised cache. */
+int chitu_hip_gqa_decode_multi(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_t, int64_t q_stride_h,
+                               const void* k_cache, const void* v_cache, int64_t num_pages, int32_t page_size,
+                               int32_t kv_heads, const int32_t* block_table, int32_t table_stride,
+                               const int32_t* seqlens, float softmax_scale, void* out_bf16, int32_t batch,
+                               int32_t q_len, int32_t q_heads, int32_t head_dim, int32_t num_splits, void* workspace,
+                               int64_t workspace_bytes, int32_t window_left, float softcap, void* stream);
+int chitu_hip_gqa_decode_multi_kv_fp8(const void* q_bf16, int64_t q_stride_b, int64_t q_stride_t, int64_t q_stride_h,
+                                      const void* k_cache, const void* v_cache, int64_t num_pages, int32_t page_size,
+                                      int32_t kv_heads, const int32_t* block_table, int32_t table_stride,
+                                      const int32_t* seqlens, float softmax_scale, void* out_bf16, int32_t batch,
+                                      int32_t q_len, int32_t q_heads, int32_t head_dim, int32_t num_splits,
+                                      void* workspace, int64_t workspace_bytes, int32_t window_left, float softcap,
+                                      void* stream);
 
 /* ---- token sampling (the step after the path) -----------------------------------
  * Replaces NormalExecutor.update_response's device work (chitu/executor.py:82-112) and
