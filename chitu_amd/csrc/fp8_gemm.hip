@@ -226,13 +226,6 @@ __global__ __launch_bounds__(64 * WK) void soft_fp8_gemm_kernel(
     gemm_epilogue<MT, WK>(acc, red, out, out_dt, partial, M, N, S, m_base, n0);
 }
 
-void launch_splitk_reduce(const float* partial, void* out, int out_dt, int S, int64_t MN, hipStream_t st) {
-    int blocks = (int)((MN / 4 + 255) / 256);
-    if (blocks < 1) blocks = 1;
-    if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, partial, out, out_dt, S, MN);
-}
-
 // from this many token rows on, the W8A8 GEMM is tiled for compute (fp8_gemm_tiled.hip) instead of streamed per 64 rows
 constexpr int kTiledMinRows = 128;
 

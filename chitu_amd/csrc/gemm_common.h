@@ -223,9 +223,6 @@ void launch_fp8_gemm_tiled(const fp8_t* a, const float* a_s, const fp8_t* b, con
 void launch_bf16_gemm_tiled(const bf16_t* x, const bf16_t* w, void* out, int out_dt, int64_t M, int64_t N, int64_t K,
                             int num_splits, float* partials, hipStream_t st);
 
-// out[m][n] = sum_s partial[s][m][n] (s ascending), cast to out_dt.  Defined in fp8_gemm.hip.
-void launch_splitk_reduce(const float* partial, void* out, int out_dt, int S, int64_t MN, hipStream_t st);
-
 // ---------------------------------------------------------------- XCD-blocked tile order (prefill-shaped GEMMs)
 // Workgroup b of a launch runs on XCD b % 8 (observed dispatch order, MI355X_MICROARCH.md: used for speed only, never for
 // correctness), and every XCD has its own 4 MB L2.  A row-major walk over a (tiles_n x tiles_m) grid therefore gives each
