@@ -30,6 +30,7 @@ def is_fp8_gqa_cache(cache) -> bool:
     return cache.dtype == torch.uint8 and cache.dim() == 4 and cache.shape[-1] == GQA_KV_FP8_ROW
 
 
+MLA_MULTI_MAX_Q = 8  # query tokens per sequence of chitu_hip_mla_decode_multi (csrc/mla_decode_tile.h: kMlaMultiMaxQ)
 GQA_MULTI_MAX_Q = 8  # query tokens per sequence of chitu_hip_gqa_decode_multi (csrc/gqa_decode_multi.hip: kGqaMultiMaxQ)
 # Upper bound of the KV splits of the GQA decode launch (graph-static: sized from the page table's width, not from the
 # lengths).  32 by the sweep of round 4 (Llama-3-8B bs 1, ctx 1024: 64 -> 3.064, 32 -> 3.041, 16 -> 3.077, 8 -> 3.175 ms/step;
@@ -88,6 +89,19 @@ def choose_num_splits(batch: int, head_blocks: int, max_tiles: int, target_wgs: 
     per = max(1, batch * head_blocks)
     s = max(1, min(max_tiles, (target_wgs + per - 1) // per))
     return min(s, 64)
+
+
+# The multi-token MLA launch against the composition it replaces (chitu_hip_mla_decode on bs * T expanded rows), measured
+# (profiles/mla_multi_sweep.json): the pair kernel reads the pages half as often but runs its two tile steps one
+# after the other, so it wins only once the composition's workgroups more than fill the chip -- at bs * T * head_blocks *
+# max_tiles = 4128 and 8256 tile steps it takes 0.76 - 0.89 of the composition's time, at 1088 the two tie, at 544 and below it
+# is 1.08 - 1.5 x slower.  The crossover, in tile steps per CU of the composition (1088 / 256 CUs):
+MLA_MULTI_MIN_TILE_STEPS_PER_CU = 4.25
+
+
+def mla_multi_beats_composition(batch: int, q_len: int, heads: int, max_tiles: int) -> bool:
+    """Graph-static routing rule of HipAttnBackend.mla_decode_multi (batch, T and the table's width: no lengths)."""
+    return batch * q_len * ((heads + 15) // 16) * max_tiles >= MLA_MULTI_MIN_TILE_STEPS_PER_CU * _num_cus()
 
 
 def window_and_cap(window_size, softcap, causal: bool):
@@ -216,6 +230,76 @@ class HipAttnBackend(AttnBackend):
                 i64(ws.numel()), stream_ptr(),
             ),
             "mla_decode_kv_fp8" if fp8_kv else "mla_decode",
+        )
+        return (ws, num_splits) if partials else out
+
+    def mla_decode_multi(self, q_nope, q_pe, kv_cache, cache_seqlens_incl, block_table, softmax_scale,
+                         num_splits: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                         return_partials: bool = False, kernel: Optional[str] = None, expanded=None):
+        """mla_decode for T = q_nope.shape[1] <= 8 query tokens per sequence (chitu_hip_mla_decode_multi / _kv_fp8 by cache dtype,
+        csrc/mla_decode_multi.hip): q_nope [bs, T, H, 512], q_pe [bs, T, H, 64]; cache_seqlens_incl [bs] counts all keys, the T
+        rows appended this step included; block_table [bs, stride], one row per sequence.  Query (b, t) sees the first
+        L - T + t + 1 keys.  Returns [bs, T, H, 512], or with return_partials and more than one split (workspace, num_splits)
+        with bs * T rows in (b, t) order: ops.mla_merge_absorb_uv_quant_fp8 consumes it with batch = bs * T.  One workgroup
+        takes two query tokens, so the splits are sized for head_blocks * ceil(T / 2) workgroups per sequence (graph-static).
+
+        kernel: "multi" = that launch; "composed" = the composition it replaces, mla_decode on the bs * T expanded rows (each
+        table row T times, lengths L - T + t + 1: the same attention, row for row); None = by the measured rule
+        mla_multi_beats_composition, T == 1 always the multi launch.  expanded = (table [bs * T, stride], lengths [bs * T]) of the
+        expanded rows where the caller has them already (the cache manager's multi-token buffers); else they are built here."""
+        require_cuda(q_nope, q_pe, kv_cache, cache_seqlens_incl, block_table)
+        assert kv_cache.ndim == 3 and kv_cache.is_contiguous()
+        fp8_kv = is_fp8_mla_cache(kv_cache)
+        assert (kv_cache.dtype == torch.bfloat16 or fp8_kv) and q_nope.dtype == torch.bfloat16 and q_pe.dtype == torch.bfloat16
+        assert block_table.dtype == torch.int32 and cache_seqlens_incl.dtype == torch.int32
+        assert block_table.stride(1) == 1 and cache_seqlens_incl.is_contiguous()
+        B, T, H, C = q_nope.shape
+        R = q_pe.shape[-1]
+        assert tuple(q_pe.shape[:3]) == (B, T, H) and (fp8_kv or kv_cache.shape[-1] == C + R)
+        assert tuple(block_table.shape)[0] == B and cache_seqlens_incl.numel() == B
+        if not 1 <= T <= MLA_MULTI_MAX_Q:
+            raise ValueError(f"mla_decode_multi: {T} query tokens per sequence; 1 .. {MLA_MULTI_MAX_Q} are implemented")
+
+        def ok(t):
+            return t.stride(-1) == 1 and all(t.stride(d) % 8 == 0 for d in range(3)) and t.data_ptr() % 16 == 0
+
+        if not ok(q_nope):
+            q_nope = q_nope.contiguous()
+        if not ok(q_pe):
+            q_pe = q_pe.contiguous()
+        max_tiles = max(1, (int(block_table.shape[1]) * int(kv_cache.shape[1]) + 63) // 64)
+        if kernel is None:
+            kernel = "multi" if T == 1 or mla_multi_beats_composition(B, T, H, max_tiles) else "composed"
+        if kernel == "composed":
+            if expanded is None:
+                steps = torch.arange(1 - T, 1, dtype=torch.int32, device=q_nope.device)
+                expanded = (block_table.repeat_interleave(T, dim=0), (cache_seqlens_incl.view(B, 1) + steps.view(1, T)).reshape(B * T))
+            table_x, lens_x = expanded
+            assert tuple(table_x.shape)[0] == B * T and lens_x.numel() == B * T
+            if num_splits is None:
+                num_splits = choose_num_splits(B * T, (H + 15) // 16, max_tiles)
+            res = self.mla_decode(q_nope.reshape(B * T, H, C), q_pe.reshape(B * T, H, R), kv_cache, lens_x, table_x, softmax_scale,
+                                  num_splits=num_splits, out=None if out is None else out.view(B * T, H, C), return_partials=return_partials)
+            return res if isinstance(res, tuple) else res.view(B, T, H, C)
+        assert kernel == "multi", kernel
+        if num_splits is None:
+            num_splits = choose_num_splits(B, ((H + 15) // 16) * ((T + 1) // 2), max_tiles)
+        partials = return_partials and num_splits > 1
+        if out is None and not partials:
+            out = torch.empty(B, T, H, C, dtype=torch.bfloat16, device=q_nope.device)
+        assert partials or (out.is_contiguous() and tuple(out.shape) == (B, T, H, C) and out.dtype == torch.bfloat16)
+        need = B * T * H * num_splits * (C * 2 + 4) if num_splits > 1 else 0  # bf16 partial rows + fp32 LSE
+        ws = workspace.get(max(need, 1), q_nope.device, "mla")
+        name = "mla_decode_multi_kv_fp8" if fp8_kv else "mla_decode_multi"
+        check(
+            getattr(_lib.lib(), "chitu_hip_" + name)(
+                ptr(q_nope), i64(q_nope.stride(0)), i64(q_nope.stride(1)), i64(q_nope.stride(2)), ptr(q_pe), i64(q_pe.stride(0)),
+                i64(q_pe.stride(1)), i64(q_pe.stride(2)), ptr(kv_cache), i64(kv_cache.shape[0]), i32(kv_cache.shape[1]),
+                ptr(block_table), i32(block_table.stride(0)), ptr(cache_seqlens_incl), f32(softmax_scale),
+                ptr(None if partials else out), i32(B), i32(T), i32(H), i32(C), i32(R), i32(num_splits), ptr(ws),
+                i64(ws.numel()), stream_ptr(),
+            ),
+            name,
         )
         return (ws, num_splits) if partials else out
 

@@ -257,10 +257,11 @@ class PagedKVCacheManager:
         Sized for MAX_DECODE_Q tokens per request, so one allocation serves every T."""
         if self._multi_dev is None:
             n, rows = self._lens_dev.shape[1], self._lens_dev.shape[1] * MAX_DECODE_Q
-            # [row lengths (rows) | lengths incl. the T new tokens (n)] in one allocation: one copy refreshes both
-            self._multi_dev = torch.zeros(rows + n, dtype=torch.int32, device=self.device)
+            # [row lengths (rows) | lengths incl. the T new tokens (n) | row lengths incl. the row itself (rows)] in one
+            # allocation: one copy refreshes all three
+            self._multi_dev = torch.zeros(2 * rows + n, dtype=torch.int32, device=self.device)
             self._multi_table_dev = torch.zeros((rows, self.max_blocks_per_req), dtype=torch.int32, device=self.device)
-            self._multi_host = torch.zeros(_STAGE_RING, rows + n, dtype=torch.int32, pin_memory=self._pinned)
+            self._multi_host = torch.zeros(_STAGE_RING, 2 * rows + n, dtype=torch.int32, pin_memory=self._pinned)
             self._multi_host_table = torch.zeros((_STAGE_RING, rows, self.max_blocks_per_req), dtype=torch.int32,
                                                  pin_memory=self._pinned)
             self._stage_events.update(multi=[None] * _STAGE_RING, multi_table=[None] * _STAGE_RING)
@@ -272,6 +273,8 @@ class PagedKVCacheManager:
         buffers of its own (the single-token step's buffers are not touched):
           get_gpu_multi_row_lens()      [n * T] the old length + t of expanded row (b, t): its RoPE and append position
           get_gpu_multi_seq_lens_incl() [n]     the old length + T: the keys the attention sees
+          get_gpu_multi_row_lens_incl() [n * T] the old length + t + 1: the keys expanded row (b, t) sees, for an attention that
+                                        takes the step as n * T single-token rows
           get_gpu_multi_block_table()   [n * T, max_blocks] request b's table in each of its T rows (the append kernels take one
                                         table row per appended row; the attention reads every T-th row)
         Pages beyond ceil(len / block_size) that a step takes and finalize_cache_multi_decode does not keep go back to the
@@ -293,7 +296,8 @@ class PagedKVCacheManager:
         for b, L0 in enumerate(lens):
             h[b * T : (b + 1) * T] = range(L0, L0 + T)
         h[rows : rows + n] = [L0 + T for L0 in lens]
-        self._multi_dev[: rows + n].copy_(self._multi_host[slot][: rows + n], non_blocking=True)
+        h[rows + n : 2 * rows + n] = h[:rows] + 1
+        self._multi_dev[: 2 * rows + n].copy_(self._multi_host[slot][: 2 * rows + n], non_blocking=True)
         self._stage_done("multi", slot)
         slot = self._stage_slot("multi_table")
         ht = self._multi_host_table[slot].numpy()
@@ -312,6 +316,10 @@ class PagedKVCacheManager:
     def get_gpu_multi_seq_lens_incl(self):
         n, T = self._multi_shape
         return self._multi_dev[n * T : n * T + n]
+
+    def get_gpu_multi_row_lens_incl(self):
+        n, T = self._multi_shape
+        return self._multi_dev[n * T + n : 2 * n * T + n]
 
     def get_gpu_multi_block_table(self):
         n, T = self._multi_shape

@@ -216,4 +216,87 @@ static inline int mla_decode_carve_workspace(void* workspace, int64_t workspace_
     return CHITU_OK;
 }
 
+// ---- the multi-token entries (mla_decode_multi.hip, mla_decode_multi_kv_fp8.hip): q_len = T <= kMlaMultiMaxQ query tokens per
+// sequence, two per workgroup.  Everything above is used as it is: a staged tile is multiplied once per token of the pair by
+// mla_tile_step with that token's own state, so a token's arithmetic and its order are the single-token kernels'.
+constexpr int kMlaMultiMaxQ = 8;  // cache_manager.MAX_DECODE_Q
+
+// blockIdx.z -> (head block, the pair's tokens t0, t1); an odd T's last pair has one token (two == false, t1 == t0)
+struct MlaPair {
+    int hb, t0, t1;
+    bool two;
+};
+__device__ __forceinline__ MlaPair mla_pair_of_block(int z, int T) {
+    const int pairs = (T + 1) >> 1;
+    MlaPair p;
+    p.hb = z / pairs;
+    p.t0 = 2 * (z % pairs);
+    p.two = p.t0 + 1 < T;
+    p.t1 = p.two ? p.t0 + 1 : p.t0;
+    return p;
+}
+
+// what one query token keeps across the tiles: its Q fragments (the A operand), accumulators and running max / sum
+struct MlaTokenState {
+    s16x8 qf[18];
+    f32x4 o[8];
+    float m_run[4], l_run[4];
+};
+__device__ __forceinline__ void mla_token_init(MlaTokenState& s) {
+#pragma unroll
+    for (int c = 0; c < 8; ++c) s.o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        s.m_run[r] = -INFINITY;
+        s.l_run[r] = 0.f;
+    }
+}
+
+// One staged tile, once per token of the pair: token k sees L_k keys, valid_k = min(64, L_k - tile * 64) of this tile's; a token
+// with none skips the step (the condition is workgroup-uniform: the barriers inside the step stay matched).  The exchange areas
+// are in use until a barrier, hence the one between the two steps.
+__device__ __forceinline__ void mla_pair_tile_steps(const uint8_t* kv, const MlaFrag& f, int tile, int L0, int L1, float scale,
+                                                    bf16_t* p_lds, float* red_max, float* red_sum, MlaTokenState& s0,
+                                                    MlaTokenState& s1, int wave, int j, int g) {
+    const int valid0 = min(kTile, L0 - tile * kTile), valid1 = min(kTile, L1 - tile * kTile);
+    if (valid0 > 0) mla_tile_step(kv, s0.qf, f, valid0, scale, p_lds, red_max, red_sum, s0.o, s0.m_run, s0.l_run, wave, j, g);
+    if (valid1 > 0) {
+        if (valid0 > 0) __syncthreads();
+        mla_tile_step(kv, s1.qf, f, valid1, scale, p_lds, red_max, red_sum, s1.o, s1.m_run, s1.l_run, wave, j, g);
+    }
+}
+
+// A token's epilogue, `row` = b * T + t: the single-token kernels' (1 / l_run, LSE = m_run + log l_run) where the token saw a
+// key in this split; where it saw none (l_run == 0), zero rows and LSE = -inf, what mla_publish_empty_split writes.
+__device__ __forceinline__ void mla_token_epilogue(const MlaTokenState& s, bf16_t* part_o, float* part_lse, bf16_t* out, bf16_t* o_lds,
+                                                   int row, int H, int h0, int split, int num_splits, int tid, int wave, int j, int g) {
+    float inv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) inv[r] = s.l_run[r] > 0.f ? 1.0f / s.l_run[r] : 0.f;
+    if (num_splits == 1) {
+        mla_store_out_rows(out, s.o, inv, row, H, h0, wave, j, g);
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int h = h0 + g * 4 + r;
+        if (wave == 0 && j == 0 && h < H)
+            part_lse[((int64_t)row * H + h) * num_splits + split] = s.l_run[r] > 0.f ? s.m_run[r] + __logf(s.l_run[r]) : -INFINITY;
+    }
+    mla_store_partial_rows(part_o, o_lds, s.o, inv, row, H, h0, split, num_splits, tid, wave, j, g);
+}
+
+// the multi-token entries' argument checks: their own BAD_ARG checks, then the shared ones
+static inline int mla_decode_multi_check_args(const void* q_nope, const void* q_pe, const void* kv_cache, const int32_t* block_table,
+                                              const int32_t* seqlens, int32_t batch, int32_t q_len, int32_t heads, int64_t num_pages,
+                                              int32_t page_size, int32_t table_stride, int32_t kv_lora_rank, int32_t rope_dim,
+                                              int32_t num_splits, int64_t qn_sb, int64_t qn_st, int64_t qn_sh, int64_t qp_sb,
+                                              int64_t qp_st, int64_t qp_sh) {
+    CHITU_REQUIRE(q_len >= 1 && q_len <= kMlaMultiMaxQ);
+    CHITU_REQUIRE(batch <= INT32_MAX / kMlaMultiMaxQ);  // batch * q_len rows
+    CHITU_REQUIRE(((qn_sb | qn_st | qn_sh | qp_sb | qp_st | qp_sh) & 7) == 0);  // 16-byte loads of q
+    return mla_decode_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, heads, num_pages, page_size, table_stride,
+                                 kv_lora_rank, rope_dim, num_splits, 1);
+}
+
 }  // namespace chitu

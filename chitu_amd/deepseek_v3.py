@@ -24,8 +24,8 @@ import torch.nn.functional as F
 
 from . import fused_moe, graphs, ops
 from . import tensor_parallel as tp
-from .attn_backend import HipAttnBackend
-from .cache_manager import PagedKVCacheManager, mla_kv_layout
+from .attn_backend import MLA_MULTI_MAX_Q, HipAttnBackend
+from .cache_manager import MAX_DECODE_Q, PagedKVCacheManager, mla_kv_layout
 
 FP8 = torch.float8_e4m3fn
 BLOCK = 128
@@ -206,16 +206,18 @@ def _wqkv_a_splits(bs: int, n: int, k: int) -> int:
 class Fp8KvStage:
     """The decode step's KV row on its way into an fp8 latent cache.  The launches that produce the row (ops.mla_q_proj,
     ops.mla_qkv_post, ops.absorb_bmm_rope_kv_fp8) append bf16 rows to a paged cache; with an fp8 cache they are pointed at
-    this one instead -- one row per sequence, page size 1, table = arange, lengths = 0, so sequence b's row lands in row b --
-    and ops.append_mla_kv_fp8 then quantises it into the real page.  One more small launch per layer; the row every
+    this one instead -- one row per row of the step, page size 1, table = arange, lengths = 0, so row b's KV row lands in row b --
+    and ops.append_mla_kv_fp8 then quantises it into the real page.  max_bs * MAX_DECODE_Q rows: a multi-token step has
+    q_len rows per sequence.  One more small launch per layer; the row every
     producer path leaves in the page is, bit for bit, the quantiser's image of the row it would have left in a bf16 cache.
     Allocated once (at construction of the decoder): a captured graph sees fixed addresses.  Shared by all layers: they
     run in turn on one stream."""
 
     def __init__(self, max_bs, device):
-        self.rows = torch.zeros(max_bs, 1, 576, dtype=torch.bfloat16, device=device)
-        self.table = torch.arange(max_bs, dtype=torch.int32, device=device).view(max_bs, 1)
-        self.lens = torch.zeros(max_bs, dtype=torch.int32, device=device)
+        n = max_bs * MAX_DECODE_Q
+        self.rows = torch.zeros(n, 1, 576, dtype=torch.bfloat16, device=device)
+        self.table = torch.arange(n, dtype=torch.int32, device=device).view(n, 1)
+        self.lens = torch.zeros(n, dtype=torch.int32, device=device)
 
 
 class AttentionDeepSeekV3(torch.nn.Module):
@@ -278,8 +280,12 @@ class AttentionDeepSeekV3(torch.nn.Module):
         """The attention's first linear -- wqkv_a, or [wq | wkv_a] of a model without a q low-rank path."""
         return self.wqkv_a if self.q_lora_rank > 0 else self.wq_kv_a
 
-    def decode_forward_paged(self, x_quant, cos, sin, first=None):
+    def decode_forward_paged(self, x_quant, cos, sin, first=None, q_len=1):
         """x_quant = fp8 (q, s) of attn_norm(x), [bs, dim].  Returns wo(attn) before the all-reduce.
+        q_len = T > 1 (DeepSeekV3Decoder.decode_multi): the bs rows are T consecutive tokens of bs / T sequences in (b, t)
+        order.  Every producer that appends takes the cache manager's multi-token table and per-row lengths (row (b, t) lands
+        at old length + t), the attention is ONE chitu_hip_mla_decode_multi call on the [bs / T, T, H, .] view, and everything
+        else runs on the rows as it does at T = 1.
         first: the first projection's output [bs, N] bf16 when the launch in front already computed it
         (ops.fp8_linear_add_norm: attn_norm as that GEMM's prologue); x_quant is then not read.
 
@@ -294,7 +300,11 @@ class AttentionDeepSeekV3(torch.nn.Module):
             bs = x_quant[0].rows if isinstance(x_quant[0], ops.TiledQuant) else x_quant[0].shape[0]
         cache = self.cache
         kv_cache = cache.get_paged_kv_cache(self.layer_id)
-        kv_table, kv_lens = cache.get_gpu_block_table(), cache.get_gpu_seq_lens_excl_this_decode()
+        if q_len > 1:
+            assert bs % q_len == 0
+            kv_table, kv_lens = cache.get_gpu_multi_block_table(), cache.get_gpu_multi_row_lens()
+        else:
+            kv_table, kv_lens = cache.get_gpu_block_table(), cache.get_gpu_seq_lens_excl_this_decode()
         paged = None
         if self.kv_fp8:  # the producers below write this step's bf16 rows to the stage; moved into the pages behind them
             paged = (kv_cache, kv_table, kv_lens)
@@ -343,16 +353,23 @@ class AttentionDeepSeekV3(torch.nn.Module):
         # decode launch, same bits, measured slower -- see _MLA_FUSED_TAIL)
         fuse_merge = bs <= 32 and C == 512
         w_uv = self.wkv_b.weight.view(H, self.qk_nope_head_dim + self.v_head_dim, C)[:, self.qk_nope_head_dim :]
-        fused = None
-        if fuse_merge and _MLA_FUSED_TAIL and self.v_head_dim == 128:
+        if q_len == 1 and fuse_merge and _MLA_FUSED_TAIL and self.v_head_dim == 128:
             fused = self.attn_backend.mla_decode_merge_uv_quant(
                 q_abs, q_pe, kv_cache, cache.get_gpu_seq_lens_incl_this_decode(), cache.get_gpu_block_table(), self.softmax_scale,
                 w_uv, self.wkv_b.scale, nblk, 2 * nblk, 1, tile_major=ops.tile_major_ok(bs))
-        if fused is not None:
-            oq, os_ = fused
-            return self.wo(None, x_quant=(oq, os_))
-        o = self.attn_backend.mla_decode(q_abs, q_pe, kv_cache, cache.get_gpu_seq_lens_incl_this_decode(),
-                                         cache.get_gpu_block_table(), self.softmax_scale, return_partials=fuse_merge)
+            if fused is not None:
+                return self.wo(None, x_quant=fused)
+        if q_len > 1:  # (no fused-tail form: the multi-token step takes the two launches; the backend picks the pair kernel or,
+            # where that was measured slower, the single-token kernel on the expanded rows)
+            o = self.attn_backend.mla_decode_multi(q_abs.view(bs // q_len, q_len, H, C), q_pe.unflatten(0, (bs // q_len, q_len)), kv_cache,
+                                                   cache.get_gpu_multi_seq_lens_incl(), cache.get_gpu_multi_block_table()[::q_len],
+                                                   self.softmax_scale, return_partials=fuse_merge,
+                                                   expanded=(cache.get_gpu_multi_block_table(), cache.get_gpu_multi_row_lens_incl()))
+            if not isinstance(o, tuple):
+                o = o.view(bs, H, C)
+        else:
+            o = self.attn_backend.mla_decode(q_abs, q_pe, kv_cache, cache.get_gpu_seq_lens_incl_this_decode(),
+                                             cache.get_gpu_block_table(), self.softmax_scale, return_partials=fuse_merge)
         # out = o . W_UV^T  (einsum "bshc,hdc->bshd", :697) + the act-quant of wo's input
         if isinstance(o, tuple):
             oq, os_ = ops.mla_merge_absorb_uv_quant_fp8(o[0], o[1], bs, w_uv, self.wkv_b.scale, nblk, 2 * nblk, 1,
@@ -548,8 +565,9 @@ class TransformerBlockDeepSeekV3(torch.nn.Module):
         self.attn_norm = RMSNormW(args.dim, args.norm_eps, device)
         self.ffn_norm = RMSNormW(args.dim, args.norm_eps, device)
 
-    def forward(self, x, pending, cos, sin, varlens=None):
-        """(x, pending) -> (x', pending'); varlens given = prefill (ragged prompt tokens), else decode.
+    def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
+        """(x, pending) -> (x', pending'); varlens given = prefill (ragged prompt tokens), else decode; q_len > 1: the rows are
+        q_len tokens per sequence (DeepSeekV3Decoder.decode_multi), which only the attention needs to know.
         The residual stream is x + pending; every residual add is folded into the RMSNorm that consumes the sum
         (`add_norm`), so a layer is norm, attention, norm, ffn with no separate add launches (reference:
         :1107-1113).  With tensor parallelism the sublayer outputs are partials: `tp.defer_all_reduce` hands
@@ -563,11 +581,11 @@ class TransformerBlockDeepSeekV3(torch.nn.Module):
             # GEMM, redone by each of its workgroups -- one launch less per layer, bit-identical
             proj = self.attn.first_projection()
             x, first = ops.fp8_linear_add_norm(x, pending, self.attn_norm.weight, self.attn_norm.eps, proj.weight, proj.scale)
-            a = tp.defer_all_reduce(self.attn.decode_forward_paged(None, cos, sin, first=first))
+            a = tp.defer_all_reduce(self.attn.decode_forward_paged(None, cos, sin, first=first, q_len=q_len))
             return self.ffn_part(x, a, cos, sin, varlens)
         x, _, xq, xs = add_norm(x, pending, self.attn_norm, out_bf16=False, quant="act", tile_major=tm)
         if varlens is None:
-            a = tp.defer_all_reduce(self.attn.decode_forward_paged((xq, xs), cos, sin))
+            a = tp.defer_all_reduce(self.attn.decode_forward_paged((xq, xs), cos, sin, q_len=q_len))
         else:
             a = tp.defer_all_reduce(self.attn.prefill_forward((xq, xs), cos, sin, varlens))
         return self.ffn_part(x, a, cos, sin, varlens)
@@ -653,17 +671,19 @@ class DeepSeekV3Decoder(torch.nn.Module):
         self.graphs, self.static_tokens, self.static_out = {}, {}, {}
         self.graph_pool = None
 
-    def decode_eager(self, tokens):
-        """tokens [bs] int64 -> logits [bs, vocab] fp32 (decode_single_device, model.py:468-475)."""
-        # embedding rows of this rank's vocabulary slice + every sequence's rotary row (prepare_freqs_cis_decode,
+    def decode_eager(self, tokens, q_len=1):
+        """tokens [bs] int64 -> logits [bs, vocab] fp32 (decode_single_device, model.py:468-475).  q_len > 1: the rows are q_len
+        consecutive tokens of each sequence, positions and page rows from the cache manager's multi-token buffers."""
+        # embedding rows of this rank's vocabulary slice + every row's rotary row (prepare_freqs_cis_decode,
         # model.py:429-448): one launch
+        positions = self.cache.get_gpu_multi_row_lens() if q_len > 1 else self.cache.get_gpu_seq_lens_excl_this_decode()
         h, cos, sin = ops.embed_rope_gather(tokens, self.embed_weight, self.vocab_start if self.vocab_local != self.args.vocab_size else 0,
-                                            self.cache.get_gpu_seq_lens_excl_this_decode(), self.cos_table, self.sin_table)
+                                            positions, self.cos_table, self.sin_table)
         if self.vocab_local != self.args.vocab_size:
             h = tp.all_reduce(h)  # tensor_parallel.py:199-208
         pending = None
         for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin)
+            h, pending = layer(h, pending, cos, sin, q_len=q_len)
         h = add_norm(h, pending, self.norm)[1]
         # bf16 logits -> fp32 (model.py:475), the cast riding in the gather
         return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
@@ -767,6 +787,63 @@ class DeepSeekV3Decoder(torch.nn.Module):
             self.graphs[key] = g
         self.graphs[key].replay()
         return self.static_out[bs]
+
+    @torch.inference_mode()
+    def decode_multi(self, tokens, use_graph=True):
+        """One step over T = tokens.shape[1] tokens per sequence (1 < T <= 8): tokens [bs, T] int64 are appended at each
+        sequence's length .. + T - 1 and token t attends to everything up to itself -- the verify step of speculative decoding
+        (LlamaDecoder.decode_multi's contract).  Returns fp32 logits [bs, T, vocab]: row (b, t) predicts the token after
+        tokens[b, t].  The caller has run cache.prepare_block_table_for_decode_multi(req_ids, T) and settles the lengths with
+        finalize_cache_multi_decode.
+
+        The stack runs on bs * T rows with per-row positions (the fused small-batch launches apply by their row limits on
+        bs * T); only the attention knows T: chitu_hip_mla_decode_multi reads each sequence's pages ceil(T / 2) times.  Graph
+        replay as in decode(), keyed (bs, T, mode), on static buffers of its own."""
+        tp.check_comm()
+        assert tokens.dim() == 2 and tokens.dtype == torch.int64
+        bs, T = tokens.shape
+        if T == 1:
+            raise ValueError("decode_multi is the multi-token step (T > 1); decode() is the single-token one")
+        if T > MLA_MULTI_MAX_Q:
+            raise ValueError(f"decode_multi: {T} tokens per sequence; 2 .. {MLA_MULTI_MAX_Q} are implemented")
+        _check_multi_step_rows(bs * T)
+        flat = tokens.reshape(bs * T)
+        if not use_graph or tp.xgmi_split_phase():
+            return self.decode_eager(flat, T).view(bs, T, -1)
+        mode = graphs.graph_mode(use_graph)
+        key, skey = (bs, T, mode), (bs, T)
+        if skey not in self.static_tokens:
+            self.static_tokens[skey] = flat.clone()
+        else:
+            self.static_tokens[skey].copy_(flat)
+        if key not in self.graphs:
+            g, self.graph_pool, self.static_out[skey] = graphs.capture_verified(
+                lambda: self.decode_eager(self.static_tokens[skey], T), self.static_out.get(skey), mode, self.graph_pool,
+                what=f"DeepSeekV3Decoder multi-token decode step bs={bs} T={T}")
+            self.graphs[key] = g
+        self.graphs[key].replay()
+        return self.static_out[skey].view(bs, T, -1)
+
+    @torch.inference_mode()
+    def generate_speculative(self, prompts, max_new_tokens, drafter, draft_len, req_ids=None, use_graph=True, temperatures=None,
+                             top_ks=None, top_ps=None, frequency_penalties=None, generator=None):
+        """Greedy generation with draft-and-verify, LlamaDecoder.generate_speculative's contract on decode_multi: the tokens
+        plain greedy generate() picks, in fewer steps when the drafter is right (drafter.propose(history, draft_len); a
+        DeepSeek-V3 checkpoint's multi-token-prediction head is such a drafter, chitu_amd.sampling.NgramDrafter another).
+        Returns [n_req, max_new_tokens] int64 and frees the requests' pages; self.speculative_stats = {"steps", "accepted",
+        "drafted"}.  Greedy only: any sampling argument raises; draft_len outside 1 .. 7 raises."""
+        from . import sampling
+
+        return sampling.generate_speculative_greedy(self, prompts, max_new_tokens, drafter, draft_len, MLA_MULTI_MAX_Q, req_ids, use_graph,
+                                                    (temperatures, top_ks, top_ps, frequency_penalties, generator))
+
+
+def _check_multi_step_rows(rows: int):
+    """Under tensor parallelism the in-graph xGMI collectives hold at most the communicator's max_rows rows."""
+    comm = tp.xgmi_comm()
+    if comm is not None and rows > comm.max_rows:
+        raise ValueError(f"a multi-token step of {rows} rows (batch * q_len) exceeds the xGMI communicator's {comm.max_rows} rows: "
+                         f"size it with tensor_parallel.enable_xgmi(max_rows >= {rows})")
 
 
 def refresh_derived_layouts(model: torch.nn.Module):

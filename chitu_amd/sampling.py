@@ -231,3 +231,57 @@ class NgramDrafter:
                     break
         fill = out[-1] if out else h[-1]
         return out + [fill] * (k - len(out))
+
+
+def generate_speculative_greedy(model, prompts, max_new_tokens, drafter, draft_len, max_q, req_ids=None, use_graph=True,
+                                sampling_args=()):
+    """The draft-and-verify loop of LlamaDecoder / DeepSeekV3Decoder.generate_speculative (their docstrings state the contract):
+    model-independent, it needs model.prefill, model.decode_multi, model.cache and model.device, and leaves
+    model.speculative_stats.  max_q: the most tokens a verify step of the model holds (the last token + max_q - 1 drafts)."""
+    from . import tensor_parallel as tp
+
+    if any(a is not None for a in sampling_args):
+        raise NotImplementedError("generate_speculative is greedy: the acceptance rule draft == argmax has no sampling form here")
+    if not 1 <= draft_len <= max_q - 1:
+        raise ValueError(f"draft_len={draft_len}: a verify step holds the last token and 1 .. {max_q - 1} drafts")
+    n_req = len(prompts)
+    req_ids = [f"gen{i}" for i in range(n_req)] if req_ids is None else list(req_ids)
+    T = draft_len + 1
+    first = argmax(model.prefill(prompts, req_ids)).tolist()
+    out = [[t] for t in first]
+    stats = {"steps": 0, "accepted": 0, "drafted": 0}
+    live = list(range(n_req))
+    if max_new_tokens <= 1:
+        live = []
+        for r in req_ids:
+            model.cache.finalize_cache_all_decode(r)
+    while live:
+        drafts = []
+        for i in live:
+            d = [int(t) for t in drafter.propose(list(prompts[i]) + out[i], draft_len)]
+            assert len(d) == draft_len, f"drafter proposed {len(d)} tokens, not draft_len={draft_len}"
+            drafts.append(d)
+        ids = [req_ids[i] for i in live]
+        model.cache.prepare_block_table_for_decode_multi(ids, T)
+        step = torch.tensor([[out[i][-1]] + d for i, d in zip(live, drafts)], dtype=torch.int64, device=model.device)
+        logits = model.decode_multi(step, use_graph=use_graph)
+        best = argmax(logits.view(len(live) * T, -1)).view(len(live), T).tolist()
+        kept = []
+        for i, d, a in zip(live, drafts, best):
+            n_ok = 0
+            while n_ok < draft_len and d[n_ok] == a[n_ok]:
+                n_ok += 1
+            out[i].extend(d[:n_ok] + [a[n_ok]])
+            kept.append(n_ok + 1)
+            stats["accepted"] += n_ok
+            stats["drafted"] += draft_len
+        stats["steps"] += 1
+        model.cache.finalize_cache_multi_decode(ids, kept)
+        for i in [i for i in live if len(out[i]) >= max_new_tokens]:
+            model.cache.finalize_cache_all_decode(req_ids[i])
+            live.remove(i)
+    model.speculative_stats = stats
+    if tp.xgmi_comm() is not None:
+        torch.cuda.current_stream().synchronize()
+        tp.check_comm()
+    return torch.tensor([o[:max_new_tokens] for o in out], dtype=torch.int64, device=model.device)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 9  /* 9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 10  /* 10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -491,6 +491,43 @@ int chitu_hip_mla_decode_kv_fp8(const void* q_nope, int64_t qn_stride_b, int64_t
                                 float softmax_scale, void* out_bf16, int32_t batch, int32_t heads,
                                 int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- Multi-token MLA paged decode (csrc/mla_decode_multi.hip, csrc/mla_decode_multi_kv_fp8.hip) ----------------------------
+ * q_len = T in 1 .. 8 query tokens per sequence over the latent cache: the verify step of speculative decoding (DeepSeek-V3's
+ * multi-token-prediction head exists for it; the reference's FlashMLA backend sizes its metadata by mtp_size,
+ * chitu/attn_backend.py:523-527).  chitu_hip_mla_decode's argument list, contract, workspace layout and limits with
+ * qn_stride_t / qp_stride_t after the batch strides and q_len after batch:
+ *   q_nope [batch, T, heads, 512], q_pe [batch, T, heads, 64] bf16 (element strides, multiples of 8, 16-byte bases);
+ *   seqlens[b] = L counts ALL keys of sequence b, the T rows appended this step included; block_table [batch, table_stride],
+ *   one row per sequence; out [batch, T, heads, 512] bf16 contiguous.
+ *   Query token t sits at position L - T + t and sees keys k <= L - T + t: query (b, t) is chitu_hip_mla_decode on a row of
+ *   length L_t = L - T + t + 1 over the same table.  L_t <= 0 gives zero rows.
+ *   One workgroup takes 16 heads x TWO query tokens x one KV split, so a sequence's pages are read ceil(T / 2) times, not T.
+ *   workspace (num_splits > 1): chitu_hip_mla_decode_workspace_bytes(batch * T, heads, num_splits), the same layout with
+ *   batch * T rows in (b, t) order -- chitu_hip_mla_merge_absorb_uv_quant_fp8[_tm] consumes it unchanged when called with
+ *   batch * T; out_bf16 == NULL leaves the partials.
+ *   q_len outside 1 .. 8: CHITU_ERR_BAD_ARG.
+ *   Bit-identity: at q_len == 1 the output and the workspace are the bits of chitu_hip_mla_decode / _kv_fp8 at the same
+ *   num_splits.  At num_splits == 1 every row (b, t) is the bits of chitu_hip_mla_decode on the expanded problem (batch * T
+ *   rows, lengths L_t).  At num_splits > 1 the same holds, workspace included, where ceil(L_t / 64) is equal for all t of a
+ *   sequence; where the tokens straddle a 64-key tile boundary the earlier tokens' split ranges are not those of their own
+ *   single-token launch and the result is equal within the attention's rounding only.
+ *   chitu_hip_mla_decode_multi          bf16 cache [num_pages, page_size, 576].
+ *   chitu_hip_mla_decode_multi_kv_fp8   656-byte fp8 rows; bit-identical to the bf16 entry on the dequantised cache. */
+int chitu_hip_mla_decode_multi(const void* q_nope, int64_t qn_stride_b, int64_t qn_stride_t, int64_t qn_stride_h,
+                               const void* q_pe, int64_t qp_stride_b, int64_t qp_stride_t, int64_t qp_stride_h,
+                               const void* kv_cache, int64_t num_pages, int32_t page_size,
+                               const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                               float softmax_scale, void* out_bf16, int32_t batch, int32_t q_len, int32_t heads,
+                               int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits,
+                               void* workspace, int64_t workspace_bytes, void* stream);
+int chitu_hip_mla_decode_multi_kv_fp8(const void* q_nope, int64_t qn_stride_b, int64_t qn_stride_t, int64_t qn_stride_h,
+                                      const void* q_pe, int64_t qp_stride_b, int64_t qp_stride_t, int64_t qp_stride_h,
+                                      const void* kv_cache, int64_t num_pages, int32_t page_size,
+                                      const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                                      float softmax_scale, void* out_bf16, int32_t batch, int32_t q_len, int32_t heads,
+                                      int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits,
+                                      void* workspace, int64_t workspace_bytes, void* stream);
 
 /* MLA absorb-mode causal prefill attention (MQA, head dims 576 / 512): the attn_varlen_func call of
  * AttentionDeepSeekV3.prefill_forward (chitu/models/model_deepseek_v3.py:589-599; chitu/attn_backend.py:39-90).

@@ -10,7 +10,14 @@ launches of the bf16 and the fp8 cache, each captured 20x in a hipGraph, the two
 min ... max per arm, and the quantising append launch (ops.append_mla_kv_fp8, the launch the fp8 mode adds per layer) timed
 the same way.  The fp8 cache holds the quantised rows of the bf16 arm's cache, so both arms attend over the same tokens.
 --step CTX [CTX ...] [--step-bs 16] [--layers 61]: the whole decode step of the R1 rank shard (tools/moe_mxfp4_ab.py --step's
-loop) with a bf16 and an fp8 cache, each format in a fresh child process; appended to --out under "whole_step"."""
+loop) with a bf16 and an fp8 cache, each format in a fresh child process; appended to --out under "whole_step".
+--multi T [T ...] [--bs 1 16] [--ctx 1024 8192] [--out profiles/mla_multi_sweep.json]: the multi-token launch
+(chitu_hip_mla_decode_multi / _kv_fp8, T query tokens per sequence, forced: kernel="multi") against the composition it replaces, chitu_hip_mla_decode on
+bs * T expanded rows -- same process, both cache formats, each arm (launch + the merge / W_UV / quant launch on bs * T rows)
+captured 20x in a hipGraph, the graphs replayed alternately; the outputs are checked equal at one split first.
+--multi-step T [T ...] [--layers 61] [--step-ctx 1024]: the whole decode step of the R1 rank shard at bs 1, decode() against
+decode_multi() at each T (its attention routed by the backend's rule), one process, the graph-replayed steps timed in alternating
+rounds; under "multi_whole_step"."""
 import argparse
 import json
 import os
@@ -25,7 +32,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("bs_pos", nargs="?", type=int, default=None, help="batch size (the original positional form)")
 ap.add_argument("--kv-format", choices=("bf16", "fp8", "ab"), default="bf16")
 ap.add_argument("--bs", type=int, nargs="*", default=None)
-ap.add_argument("--ctx", type=int, nargs="*", default=[1024, 4096, 8192, 32768])
+ap.add_argument("--ctx", type=int, nargs="*", default=None, help="contexts (default 1024 4096 8192 32768; with --multi 1024 8192)")
 ap.add_argument("--repeats", type=int, default=15)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--out", default=None)
@@ -34,7 +41,12 @@ ap.add_argument("--step-bs", type=int, default=16)
 ap.add_argument("--layers", type=int, default=61)
 ap.add_argument("--steps", type=int, default=24)
 ap.add_argument("--child-step", default=None, help=argparse.SUPPRESS)
+ap.add_argument("--multi", type=int, nargs="*", default=None, help="query tokens per sequence of the multi-token launch A/B")
+ap.add_argument("--multi-step", type=int, nargs="*", default=None, help="T values of the whole-step decode_multi vs decode timing (bs 1)")
+ap.add_argument("--step-ctx", type=int, default=1024)
 a = ap.parse_args()
+if a.ctx is None:
+    a.ctx = [1024, 8192] if a.multi else [1024, 4096, 8192, 32768]
 
 
 def merge_into_out(key, value):
@@ -260,8 +272,125 @@ def sweep_one(bs, fmt):
         torch.cuda.empty_cache()
 
 
+@torch.inference_mode()
+def sweep_multi():
+    g = torch.Generator(device="cuda").manual_seed(0)
+    w_uv = (torch.randn(H, 128, C, device="cuda", generator=g) * 0.5).to(torch.float8_e4m3fn)
+    sc = torch.rand(H * 2, C // 128, device="cuda", generator=g) * 0.02 + 0.01
+    rows, per = [], 20
+    for bs in (a.bs or [1, 16]):
+        for ctx in a.ctx:
+            c16, table, lens, _, _ = make_inputs(bs, ctx, g)
+            c8 = ops.mla_kv_quant_fp8(c16.view(-1, C + R)).view(c16.shape[0], 64, -1)
+            be = HipAttnBackend(local_n_heads=H, max_seq_len=ctx + 64)
+            for T in a.multi:
+                q_nope = torch.randn(bs, T, H, C, device="cuda", generator=g).to(torch.bfloat16)
+                q_pe = torch.randn(bs, T, H, R, device="cuda", generator=g).to(torch.bfloat16)
+                # the expanded problem: bs * T rows, each table row T times, lengths L - T + t + 1
+                qn_x, qp_x = q_nope.view(bs * T, H, C), q_pe.view(bs * T, H, R)
+                table_x = table.repeat_interleave(T, dim=0).contiguous()
+                lens_x = (lens.view(bs, 1) - T + 1 + torch.arange(T, device="cuda", dtype=torch.int32).view(1, T)).reshape(-1).contiguous()
+
+                def tail(o):
+                    if isinstance(o, tuple):
+                        return ops.mla_merge_absorb_uv_quant_fp8(o[0], o[1], bs * T, w_uv, sc, 4, 8, 1)
+                    return ops.absorb_uv_quant_fp8(o.view(bs * T, H, C), w_uv, sc, 4, 8, 1)
+
+                def multi(cache, partials=True):
+                    return be.mla_decode_multi(q_nope, q_pe, cache, lens, table, 0.1, return_partials=partials, kernel="multi")
+
+                def composed(cache, partials=True):
+                    return be.mla_decode(qn_x, qp_x, cache, lens_x, table_x, 0.1, return_partials=partials,
+                                         num_splits=None if partials else 1)
+
+                row = {"bs": bs, "ctx": ctx, "T": T}
+                for fmt, cache, nbytes in (("bf16", c16, (C + R) * 2), ("fp8", c8, 656)):
+                    same = torch.equal(be.mla_decode_multi(q_nope, q_pe, cache, lens, table, 0.1, num_splits=1, kernel="multi").view(bs * T, H, C),
+                                       composed(cache, partials=False))
+                    om, oc = multi(cache), composed(cache)
+                    graphs = {"multi": capture(lambda: multi(cache), per), "composed": capture(lambda: composed(cache), per),
+                              "multi_tail": capture(lambda: tail(multi(cache)), per), "composed_tail": capture(lambda: tail(composed(cache)), per)}
+                    us = alternate(graphs, per)
+                    r = {k: stats(v) for k, v in us.items()}
+                    r["equal_at_one_split"] = bool(same)
+                    r["splits"] = {"multi": om[1] if isinstance(om, tuple) else 1, "composed": oc[1] if isinstance(oc, tuple) else 1}
+                    r["kv_MB_read"] = {"multi": round(bs * ctx * nbytes * ((T + 1) // 2) / 1e6, 2), "composed": round(bs * ctx * nbytes * T / 1e6, 2)}
+                    r["multi_over_composed"] = round(r["multi"]["median_us"] / r["composed"]["median_us"], 4)
+                    r["multi_over_composed_with_tail"] = round(r["multi_tail"]["median_us"] / r["composed_tail"]["median_us"], 4)
+                    row[fmt] = r
+                    del graphs
+                print(json.dumps(row), flush=True)
+                rows.append(row)
+            del c16, c8
+            torch.cuda.empty_cache()
+    merge_into_out("multi_sweep", rows)
+
+
+@torch.inference_mode()
+def multi_whole_step():
+    """ms per step of the R1 TP=8 rank shard at bs 1: decode() and decode_multi() at each T of --multi-step, graph replays,
+    alternating rounds in one process (synthetic weights, random bf16 cache)"""
+    import time
+
+    from chitu_amd.cache_manager import PagedKVCacheManager, mla_kv_layout
+    from chitu_amd.deepseek_v3 import DeepSeekV3Args, DeepSeekV3Decoder, init_synthetic_
+
+    torch.cuda.set_device(0)
+    margs = DeepSeekV3Args(shard_degree=8, n_layers=a.layers)
+    rounds, per_round = 4, max(2, a.steps // 4)
+    max_seq = a.step_ctx + (rounds + 2) * per_round * (1 + sum(a.multi_step)) + 256
+    shape, dtype = mla_kv_layout("bf16", margs.kv_lora_rank, margs.qk_rope_head_dim)
+    cache = PagedKVCacheManager(0, margs.n_layers, num_hot_req=1, block_size=64, max_seq_len=max_seq, device="cuda",
+                                kv_shape_per_sample=shape, dtype=dtype)
+    model = DeepSeekV3Decoder(margs, cache, HipAttnBackend(local_n_heads=margs.n_heads // 8, max_seq_len=max_seq),
+                              max_position_embeddings=max(max_seq, 4097), device="cuda")
+    init_synthetic_(model, seed=1000)
+    cache.paged_kv_cache.copy_(torch.randn(cache.paged_kv_cache.shape, device="cuda", dtype=torch.bfloat16) * 0.5)
+    reqs = ["r0"]
+    cache.register_sequence(reqs[0], a.step_ctx)
+    gt = torch.Generator(device="cuda").manual_seed(5)
+
+    def run(T, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            tok = torch.randint(100, 1000, (1, T), device="cuda", generator=gt)
+            if T == 1:
+                cache.prepare_cache_decode(reqs)
+                cache.prepare_block_table_for_decode(reqs)
+                model.decode(tok.view(1), use_graph=True)
+                cache.finalize_cache_single_decode(reqs)
+            else:
+                cache.prepare_block_table_for_decode_multi(reqs, T)
+                model.decode_multi(tok, use_graph=True)
+                cache.finalize_cache_multi_decode(reqs, [T])
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n * 1e3
+
+    Ts = [1] + list(a.multi_step)
+    for T in Ts:
+        run(T, 3)
+    ms = {T: [] for T in Ts}
+    for _ in range(rounds):
+        for T in Ts:
+            ms[T].append(run(T, per_round))
+    res = {"bs": 1, "ctx": a.step_ctx, "layers": a.layers, "steps_per_round": per_round, "rounds": rounds,
+           "note": "random tokens per step: T tokens route to up to T x 8 distinct experts per layer"}
+    base = statistics.median(ms[1])
+    for T in Ts:
+        m = statistics.median(ms[T])
+        res[f"T={T}"] = {"ms_per_step": round(m, 4), "min": round(min(ms[T]), 4), "max": round(max(ms[T]), 4),
+                         "ms_per_token": round(m / T, 4), "step_over_T1": round(m / base, 4)}
+    print(json.dumps(res), flush=True)
+    merge_into_out("multi_whole_step", res)
+
+
 if __name__ == "__main__":
-    if a.child_step:
+    if a.multi_step:
+        multi_whole_step()
+    elif a.multi:
+        sweep_multi()
+    elif a.child_step:
         child_step(a.child_step, a.step[0])
     elif a.kv_format == "ab":
         sweep_ab()
