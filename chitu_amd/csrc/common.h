@@ -138,9 +138,11 @@ __device__ __forceinline__ float group_rcp(float sc) {
     const float r0 = __builtin_amdgcn_rcpf(sc);
     return __builtin_fmaf(__builtin_fmaf(-sc, r0, 1.0f), r0, r0);
 }
+// The residual of x = -0 is +0 and the correction would return +0 where IEEE division gives -0: the quotient takes x's sign
+// (sc > 0 on this path), which is a no-op for every other x.
 __device__ __forceinline__ float group_div(float x, float sc, float r) {
     const float q = x * r;
-    return __builtin_fmaf(__builtin_fmaf(-q, sc, x), r, q);
+    return __builtin_copysignf(__builtin_fmaf(__builtin_fmaf(-q, sc, x), r, q), x);
 }
 
 // 8 values of one lane -> 8 e4m3 bytes of v / sc (SAT: clamped to +-448 first).

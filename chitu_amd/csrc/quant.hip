@@ -128,6 +128,13 @@ __global__ __launch_bounds__(256) void weight_dequant_kernel(const fp8_t* __rest
         } else {
             uint16_t* dst = (uint16_t*)y + row * N + n0;
             uint16_t h[16];
+            // f16: keep the fp32 product as a value of its own.  Left to itself the compiler folds multiply and conversion
+            // into v_fma_mixlo_f16 x, s, 0, which rounds once (the reference rounds the fp32 product, then to f16) and
+            // turns the product -0 (code 0x80) into +0.
+            if (OUT_DT == 1) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) asm volatile("" : "+v"(v[i]));
+            }
 #pragma unroll
             for (int i = 0; i < 16; ++i) h[i] = OUT_DT == 0 ? f32_to_bf16(v[i]) : f32_to_f16(v[i]);
             if (full) {

@@ -36,23 +36,40 @@ def to_out(t, dtype):
     return CAST["out"](t, dtype)
 
 
+def _amax_dropping_nan(xf: torch.Tensor) -> torch.Tensor:
+    """tl.max(tl.abs(x)): Triton's max reduction combines with tl.maximum, whose default propagate_nan is
+    tl.PropagateNan.NONE -- a NaN operand is dropped, the other operand is the result (IEEE maxNum).  The group maximum is
+    therefore the maximum over the elements that are not NaN (0 if all are); an infinity stays.  (Read off the kernel text and
+    Triton's documented defaults; no Triton run stands behind it.)"""
+    a = xf.abs()
+    return torch.where(torch.isnan(a), torch.zeros_like(a), a).amax(dim=-1)
+
+
 def act_quant_deepseek_v3(x: torch.Tensor, block_size: int = BLOCK):
-    """chitu/triton_kernels.py:193-214: s = max|x|/448 (no eps), y = (x/s) -> e4m3fn (no clamp)."""
+    """chitu/triton_kernels.py:193-214: s = max|x|/448 (no eps), y = (x/s) -> e4m3fn (no clamp).
+    Non-finite inputs: the maximum drops NaN (see _amax_dropping_nan), so one NaN among finite values leaves the scale and
+    every other code as they were and its own code is NaN; an infinity makes the scale infinite, the finite elements
+    (signed) zero and the infinite ones NaN (inf / inf)."""
     shape = x.shape
     xf = x.float().reshape(-1, block_size)
-    s = xf.abs().amax(dim=-1) / np.float32(FP8_MAX)
+    s = _amax_dropping_nan(xf) / np.float32(FP8_MAX)
     y = xf / s[:, None]
     q = to_fp8(y).reshape(shape)
     return q, s.reshape(*shape[:-1], shape[-1] // block_size)
 
 
 def per_token_group_quant_fp8(x: torch.Tensor, group_size: int = BLOCK, eps: float = 1e-10):
-    """chitu/fused_moe.py:670-710: s = max(max|x|, eps)/448, q = clamp(x/s, -448, 448)."""
+    """chitu/fused_moe.py:670-710: s = max(max|x|, eps)/448, q = clamp(x/s, -448, 448).
+    Non-finite inputs, as the kernel text reads (fused_moe.py:705-707): `tl.maximum(tl.max(tl.abs(y)), eps)` drops NaN
+    twice over (see _amax_dropping_nan), and `tl.clamp(y / y_s, fp8_min, fp8_max)` -- also propagate_nan NONE -- is
+    min(max(v, fp8_min), fp8_max) with NaN-dropping max and min: a NaN quotient (a NaN input, or inf / inf) becomes
+    fp8_min = -448, NOT NaN.  torch.clamp would keep the NaN, so it is replaced before the clamp here."""
     shape = x.shape
     xf = x.float().reshape(-1, group_size)
-    amax = torch.clamp(xf.abs().amax(dim=-1), min=eps)
+    amax = torch.clamp(_amax_dropping_nan(xf), min=eps)
     s = amax / np.float32(FP8_MAX)
-    y = torch.clamp(xf / s[:, None], -FP8_MAX, FP8_MAX)
+    y = xf / s[:, None]
+    y = torch.clamp(torch.where(torch.isnan(y), torch.full_like(y, -FP8_MAX), y), -FP8_MAX, FP8_MAX)
     q = to_fp8(y).reshape(shape)
     return q, s.reshape(*shape[:-1], shape[-1] // group_size)
 
