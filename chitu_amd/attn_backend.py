@@ -237,7 +237,7 @@ class HipAttnBackend(AttnBackend):
                          num_splits: Optional[int] = None, out: Optional[torch.Tensor] = None,
                          return_partials: bool = False, kernel: Optional[str] = None, expanded=None):
         """mla_decode for T = q_nope.shape[1] <= 8 query tokens per sequence (chitu_hip_mla_decode_multi / _kv_fp8 by cache dtype,
-        csrc/mla_decode_multi.hip): q_nope [bs, T, H, 512], q_pe [bs, T, H, 64]; cache_seqlens_incl [bs] counts all keys, the T
+        the kTok = 2 kernels of csrc/mla_decode.hip / mla_decode_kv_fp8.hip): q_nope [bs, T, H, 512], q_pe [bs, T, H, 64]; cache_seqlens_incl [bs] counts all keys, the T
         rows appended this step included; block_table [bs, stride], one row per sequence.  Query (b, t) sees the first
         L - T + t + 1 keys.  Returns [bs, T, H, 512], or with return_partials and more than one split (workspace, num_splits)
         with bs * T rows in (b, t) order: ops.mla_merge_absorb_uv_quant_fp8 consumes it with batch = bs * T.  One workgroup

@@ -169,7 +169,7 @@ __device__ __forceinline__ i32x2 quant8_fp8(const float (&v)[8], float sc) {
 }
 
 // One term of the MLA split merge, acc + w_s * v_s, as ONE fused multiply-add spelt out: the three merge forms (mla_merge_kernel,
-// mla_merge_uv_quant_kernel, the fused tail of mla_decode_kernel<true>) are bit-identical to each other by construction, not by
+// mla_merge_uv_quant_kernel, the fused tail of mla_decode_kernel<1, true>) are bit-identical to each other by construction, not by
 // the compiler happening to contract (or pack) `acc += w * v` the same way in three places.  A split without tokens (w = 0) adds
 // exactly 0 whatever its row holds.
 __device__ __forceinline__ float merge_term(float acc, float ws, float v) { return __builtin_fmaf(ws, ws != 0.f ? v : 0.f, acc); }

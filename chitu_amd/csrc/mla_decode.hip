@@ -37,7 +37,7 @@ namespace chitu {
 // register-staged 13.29 us, DMA 12.07, DMA + nt 11.52; ctx 8192: 36.1 -> 27.1 us).
 //
 // The tile image: mla_decode_tile.h.
-constexpr int kDmaPieces = kTileU / 1024 / 4;  // 18 per wave
+constexpr int kDmaPieces = kTileU / 1024 / 4;  // 18 per wave and tile
 
 // ---- Round 6: the split merge + W_UV projection + act_quant INSIDE the decode launch (FUSED = true).
 //
@@ -217,24 +217,48 @@ __device__ __forceinline__ void mla_fused_tail(const MlaFuse& f, MlaUvW& uw, con
     }
 }
 
-template <bool FUSED>
+using MlaLdsBf16 = MlaLds<2 * kTileU>;  // two tile images
+
+// kTok = 1: grid (num_splits, batch, ceil(heads / 16)), query row b.  kTok = 2 (q_len = T <= 8 query tokens per sequence, the verify
+// step of speculative decoding): one workgroup = 16 heads x TWO query tokens x one KV split; grid z = ceil(heads / 16) *
+// ceil(T / 2), query rows b * T + t.  seqlens[b] = L counts ALL keys, the T rows appended this step included: token t sits at
+// position L - T + t and sees L_t = L - T + t + 1 keys (<= 0: zero rows).  A tile is staged once and multiplied once per token
+// of the pair with that token's own state and valid = min(64, L_t - tile * 64) (mla_pair_tile_steps), so a sequence's pages are
+// read ceil(T / 2) times instead of T times.  The split range and the DMA's row clamp come from L, the longest length: rows in
+// [L_t, L) are real rows whose probability is exactly 0 for token t.
+//
+// What the two-token form is bit-identical to (tests/test_gpu_mla_multi.py):
+//   q_len == 1                     output and workspace are the bits of kTok = 1 at the same num_splits.
+//   num_splits == 1, any T         row (b, t) is the bits of kTok = 1 on the expanded problem (batch * T rows, each table row
+//                                  repeated T times, lengths L_t).
+//   num_splits > 1, all tokens of a sequence ending in one 64-key tile (ceil(L_t / 64) equal for all t): rows and workspace
+//                                  partials are the bits of the expanded call -- the split ranges coincide.
+//   num_splits > 1, tokens straddling a tile boundary: the earlier tokens' split ranges are those of ceil(L / 64) tiles, not of
+//                                  their own single-token launch (ceil(L_t / 64)); the result is the same attention summed in
+//                                  another grouping, equal within the attention bar only (no bit claim).
+// Registers: two tokens cost 2 x (72 Q + 32 accumulator + 8 state); with one wave per SIMD (launch bound 256, 1) the 512
+// registers hold them beside the addressing: no scratch (tests/test_flash_asm_audit.py).
+template <int kTok, bool FUSED>
 __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
-    const bf16_t* __restrict__ q_nope, int64_t qn_sb, int64_t qn_sh, const bf16_t* __restrict__ q_pe,
-    int64_t qp_sb, int64_t qp_sh, const bf16_t* __restrict__ cache, int64_t num_pages, int page_size,
+    const bf16_t* __restrict__ q_nope, MlaQStride<kTok> qn, const bf16_t* __restrict__ q_pe, MlaQStride<kTok> qp,
+    const bf16_t* __restrict__ cache, int64_t num_pages, int page_size,
     const int32_t* __restrict__ block_table, int table_stride, const int32_t* __restrict__ seqlens,
     float scale, bf16_t* __restrict__ part_o, float* __restrict__ part_lse, bf16_t* __restrict__ out,
-    int H, int num_splits, MlaFuse fuse) {
+    int H, int num_splits, MlaFuse fuse, MlaQLen<kTok> ql) {
+    static_assert(kTok == 1 || (kTok == 2 && !FUSED));
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint8_t* kv_lds = smem;                                               // [2][64][kRowU]
-    bf16_t* p_lds = reinterpret_cast<bf16_t*>(smem + 2 * kTileU);         // [16][72]
-    float* red_max = reinterpret_cast<float*>(smem + 2 * kTileU + 16 * kPStride * 2);  // [4][16]
-    float* red_sum = red_max + 64;                                        // [4][16]
-    int* pages_lds = reinterpret_cast<int*>(red_sum + 64);                // [kMaxTilesLds]
+    uint8_t* kv_lds = smem;  // [2][64][kRowU]
+    bf16_t* p_lds = reinterpret_cast<bf16_t*>(smem + MlaLdsBf16::kP);
+    float* red_max = reinterpret_cast<float*>(smem + MlaLdsBf16::kRedMax);
+    float* red_sum = reinterpret_cast<float*>(smem + MlaLdsBf16::kRedSum);
+    int* pages_lds = reinterpret_cast<int*>(smem + MlaLdsBf16::kPages);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int j = lane & 15, g = lane >> 4;
-    const int split = blockIdx.x, b = blockIdx.y, hb = blockIdx.z;
-    const int h0 = hb * 16;
+    const int split = blockIdx.x, b = blockIdx.y, T = mla_q_len(ql);
+    const MlaPair pr = mla_pair_of_block<kTok>((int)blockIdx.z, T);
+    const int hb = pr.hb, h0 = hb * 16;
+    const int row0 = b * T + pr.t0, row1 = b * T + pr.t1;  // the query rows of this workgroup's tokens (kTok = 1: b)
     const int32_t* tbl = block_table + (int64_t)b * table_stride;
     const int max_page_idx = table_stride - 1;
     // The chain that heads this kernel is seqlens -> KV rows: the table's first 256 entries are requested with seqlens,
@@ -248,29 +272,30 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         asm volatile("global_load_dword %0, %1, off" : "=v"(spec[k]) : "v"(tbl + min(lane + 64 * k, max_page_idx)) : "memory");
-    // Q (16 heads x 576): 1152 chunks of 16 B, <= 5 per thread, coalesced; it passes through buffer 1 (free until the second
-    // tile is requested) on its way to the registers of the four waves, each of which needs all of it as the A operand
-    i32x4 qreg[5];
+    // Q (per token 16 heads x 576): 1152 chunks of 16 B, <= 5 per thread and token, coalesced; it passes through buffer 1 (free
+    // until the second tile is requested) on its way to the registers of the four waves, each of which needs all of it as the A
+    // operand.  (An odd T's last workgroup reads its one token twice and uses it once.)
+    i32x4 qreg[kTok][5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int c = min(tid + i * 256, 16 * 72 - 1);
-        const int row = c / 72, col = c % 72;
-        const int h = min(h0 + row, H - 1);
-        const bf16_t* src = col < 64 ? q_nope + b * qn_sb + h * qn_sh + col * 8 : q_pe + b * qp_sb + h * qp_sh + (col - 64) * 8;
-        qreg[i] = *reinterpret_cast<const i32x4*>(src);
-    }
+    for (int k = 0; k < kTok; ++k)
+#pragma unroll
+        for (int i = 0; i < 5; ++i)
+            qreg[k][i] = *reinterpret_cast<const i32x4*>(
+                mla_q_chunk_src<kTok>(q_nope, qn, q_pe, qp, b, k ? pr.t1 : pr.t0, h0, H, min(tid + i * 256, 16 * 72 - 1)));
     asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(L_raw)::"memory");
     CHITU_PROBE_MARK(9);
     const int L = max(L_raw, 0);  // a corrupt negative length is an empty sequence
-    const int n_tiles = (L + kTile - 1) / kTile;
-    const int tile0 = (int)((unsigned)n_tiles * (unsigned)split / (unsigned)num_splits);
-    const int tile1 = (int)((unsigned)n_tiles * (unsigned)(split + 1) / (unsigned)num_splits);
-    const bool pages_in_lds = (tile1 - tile0) <= kMaxTilesLds;
+    const int Lt0 = L - T + pr.t0 + 1;               // keys token t0 sees (<= 0: none; kTok = 1: L)
+    const int Lt1 = pr.two ? L - T + pr.t1 + 1 : 0;  // the pair's second token; an odd T's last workgroup has none
+    const MlaSplit sp = mla_split_range(L, split, num_splits);
+    const int tile0 = sp.tile0, tile1 = sp.tile1;
     const int p_first = (tile0 * kTile) / page_size;
     // the table entries have landed (and Q, requested just behind them: same round trip, nothing lost)
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(spec[0]), "+v"(spec[1]), "+v"(spec[2]), "+v"(spec[3])::"memory");
 #pragma unroll
-    for (int i = 0; i < 5; ++i) asm volatile("" : "+v"(qreg[i]));  // (the compiler's own wait for Q sits here, not behind the DMA below)
+    for (int k = 0; k < kTok; ++k)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) asm volatile("" : "+v"(qreg[k][i]));  // (the compiler's own wait for Q sits here, not behind the DMA below)
     int first_pg;
     if (p_first < 256) {
         const int pick = p_first < 64 ? spec[0] : p_first < 128 ? spec[1] : p_first < 192 ? spec[2] : spec[3];
@@ -278,13 +303,9 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
     } else {
         first_pg = tbl[min(p_first, max_page_idx)];
     }
-    auto page_src = [&](int64_t page, int t0) -> const bf16_t* {
-        if (page < 0 || page >= num_pages) page = 0;  // corrupt table: stay in bounds
-        return cache + (page * page_size + (t0 % page_size)) * (int64_t)kD;
-    };
-    auto tile_src = [&](int tile) -> const bf16_t* {
-        const int t0 = tile * kTile;
-        return page_src(pages_in_lds ? pages_lds[tile - tile0] : tbl[min(t0 / page_size, max_page_idx)], t0);
+    const uint8_t* cache_u = reinterpret_cast<const uint8_t*>(cache);
+    auto tile_src = [&](int tile) {
+        return mla_tile_src(cache_u, kRowU, num_pages, page_size, tbl, max_page_idx, pages_lds, sp.pages_in_lds, tile, tile0);
     };
     // this wave's 18 pieces of a tile: piece n = wave + 4 i; lane's image chunk 64 n + lane -> (row, source byte offset)
     int prow[kDmaPieces];
@@ -296,9 +317,10 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
         pswz[i] = (uint32_t)(((qi % 72) ^ kv_swz(prow[i])) << 4);
     }
     const uint32_t lds0 = lds_offset_of(smem);
-    // rows past the sequence end re-read the tile's last valid row: finite, and their probabilities are exactly 0
-    auto issue = [&](const bf16_t* src, int valid, int buf) {
-        const bf16_t* sb = uniform_ptr(src);
+    // rows past the sequence end (L: the longest length of a pair) re-read the tile's last valid row: finite, and their
+    // probabilities are exactly 0
+    auto issue = [&](const uint8_t* src, int valid, int buf) {
+        const uint8_t* sb = uniform_ptr(src);
 #pragma unroll
         for (int i = 0; i < kDmaPieces; ++i)
             glds16_sbase<true>(sb, (uint32_t)(min(prow[i], valid - 1) * kRowU) + pswz[i],
@@ -307,46 +329,47 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
     // FUSED: an empty split still has a head of the tail to do -- it runs the rest of the kernel over zero tiles (zero rows, LSE = -inf)
     const bool empty = FUSED && tile0 >= tile1;
     if (!FUSED && tile0 >= tile1) {  // an empty split publishes LSE = -inf and zero rows (nothing of it is read by the merge)
-        mla_publish_empty_split(part_o, part_lse, out, b, H, h0, split, num_splits, tid);
+        mla_publish_empty_split(part_o, part_lse, out, row0, H, h0, split, num_splits, tid);
+        if (kTok == 2 && pr.two) mla_publish_empty_split(part_o, part_lse, out, row1, H, h0, split, num_splits, tid);
         return;
     }
-    if (!empty) issue(page_src(first_pg, tile0 * kTile), min(kTile, L - tile0 * kTile), 0);
+    if (!empty) issue(mla_page_src(cache_u, kRowU, num_pages, page_size, first_pg, tile0 * kTile), min(kTile, L - tile0 * kTile), 0);
     // FUSED: this workgroup's head of the tail (split s -> head s) -- its 64 KB of W_UV are requested once the LAST KV tile has
     // landed (no DMA is issued behind them: the counted waits stay what they are) and arrive while that tile is multiplied
     MlaUvW uvw;
     const bool uv_mine = FUSED && num_splits > 1 && split < min(16, H - h0);
     if (empty && uv_mine) mla_uv_load(uvw, fuse, h0 + split, wave, j, g);
-    {   // Q into buffer 1, in the tile image's own layout (row = head, chunk c at c ^ swz(row)): read back like a K fragment
+    {   // Q into buffer 1, in the tile image's own layout (row = head, chunk c at c ^ swz(row)): read back like a K fragment.
+        // Token k's 16 heads are rows 16 k .. 16 k + 15 (kv_swz reads bits 1 and 3 of the row, so both blocks swizzle alike)
         uint8_t* q_lds = kv_lds + kTileU;
 #pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int c = tid + i * 256;
-            if (c < 16 * 72) mla_q_store(q_lds, c, qreg[i]);
-        }
-    }
-    // page ids of the following tiles (none at one tile per split, the short-context shape: no table load, and no wait of the
-    // compiler's for one -- which, counting in order, would also wait for the tile requested above)
-    if (pages_in_lds && tile1 - tile0 > 1) {
+        for (int k = 0; k < kTok; ++k)
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
-            if (tid + i * 256 < tile1 - tile0)
-                pages_lds[tid + i * 256] = tbl[min(((tile0 + tid + i * 256) * kTile) / page_size, max_page_idx)];
+            for (int i = 0; i < 5; ++i) {
+                const int c = tid + i * 256;
+                if (c < 16 * 72) mla_q_store(q_lds + k * 16 * kRowU, c, qreg[k][i]);
+            }
     }
+    mla_fill_page_list(pages_lds, tbl, max_page_idx, page_size, sp, tid);  // the following tiles' page ids
 
-    f32x4 o[8];
+    f32x4 o[kTok][8];
+    float m_run[kTok][4], l_run[kTok][4];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[4], l_run[4];
+    for (int k = 0; k < kTok; ++k) {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        m_run[r] = -INFINITY;
-        l_run[r] = 0.f;
+        for (int c = 0; c < 8; ++c) o[k][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            m_run[k][r] = -INFINITY;
+            l_run[k][r] = 0.f;
+        }
     }
     const MlaFrag frag = mla_frag(wave, j, g);
 
     __syncthreads();  // Q and the page list are visible (the first tile may still be in flight)
-    s16x8 qf[18];
-    mla_q_frags(qf, kv_lds + kTileU, j, g);
+    s16x8 qf[kTok][18];
+#pragma unroll
+    for (int k = 0; k < kTok; ++k) mla_q_frags(qf[k], kv_lds + kTileU + k * 16 * kRowU, j, g);
     if (tile0 + 1 < tile1) {
         __syncthreads();  // every wave has its copy of Q: buffer 1 may be overwritten
         issue(tile_src(tile0 + 1), min(kTile, L - (tile0 + 1) * kTile), 1);
@@ -354,7 +377,6 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
 
     for (int tile = tile0; tile < tile1; ++tile) {
         const int buf = (tile - tile0) & 1;
-        const int valid = min(kTile, L - tile * kTile);
         if (tile == tile0 && tile0 + 1 < tile1)
             asm volatile("s_waitcnt vmcnt(18)" ::: "memory");  // the first tile's pieces; the second tile's 18 stay in flight
         else
@@ -364,32 +386,44 @@ __global__ __launch_bounds__(256, 1) void mla_decode_kernel(
         if (FUSED && tile + 1 == tile1 && uv_mine) mla_uv_load(uvw, fuse, h0 + split, wave, j, g);
         const uint8_t* kv = kv_lds + buf * kTileU;
         CHITU_PROBE_MARK(10);
-        mla_tile_step(kv, qf, frag, valid, scale, p_lds, red_max, red_sum, o, m_run, l_run, wave, j, g);
+        if constexpr (kTok == 1)
+            mla_tile_step(kv, qf[0], frag, min(kTile, L - tile * kTile), scale, p_lds, red_max, red_sum, o[0], m_run[0],
+                          l_run[0], wave, j, g);
+        else
+            mla_pair_tile_steps(kv, frag, tile, Lt0, Lt1, scale, p_lds, red_max, red_sum, qf, o, m_run, l_run, wave, j, g);
     }
 
     CHITU_PROBE_MARK(12);
-    float inv[4];
+    // (the partial transpose goes through the first buffer: at an odd tile count the last tile was multiplied there, and
+    // mla_store_partial_rows meets before it writes)
+    bf16_t* o_lds = reinterpret_cast<bf16_t*>(kv_lds);
+    if constexpr (kTok == 2) {
+        mla_token_epilogue(o[0], m_run[0], l_run[0], part_o, part_lse, out, o_lds, row0, H, h0, split, num_splits, tid, wave, j, g);
+        if (pr.two) mla_token_epilogue(o[1], m_run[1], l_run[1], part_o, part_lse, out, o_lds, row1, H, h0, split, num_splits, tid, wave, j, g);
+    } else {  // every key of a non-empty split is one the token sees: 1 / l_run needs no guard
+        float inv[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) inv[r] = empty ? 0.f : 1.0f / l_run[r];
-    if (num_splits == 1) {
-        mla_store_out_rows(out, o, inv, b, H, h0, wave, j, g);
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {  // the fp32 LSE of the split's rows
-        const int h = h0 + g * 4 + r;
-        if (wave == 0 && j == 0 && h < H) {
-            float* lp = part_lse + ((int64_t)b * H + h) * num_splits + split;
-            const float lv = empty ? -INFINITY : m_run[r] + __logf(l_run[r]);
-            if (FUSED) __hip_atomic_store(lp, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through, like the rows
-            else *lp = lv;
+        for (int r = 0; r < 4; ++r) inv[r] = empty ? 0.f : 1.0f / l_run[0][r];
+        if (num_splits == 1) {
+            mla_store_out_rows(out, o[0], inv, b, H, h0, wave, j, g);
+            return;
         }
-    }
-    mla_store_partial_rows(part_o, reinterpret_cast<bf16_t*>(kv_lds), o, inv, b, H, h0, split, num_splits, tid, wave, j, g);
-    CHITU_PROBE_MARK(13);
-    if (FUSED) {
-        // scratch: the second tile buffer's first bytes (the partial transpose above used the first buffer's)
-        mla_fused_tail(fuse, uvw, part_o, part_lse, b, H, h0, split, num_splits, b * (int)gridDim.z + hb, kv_lds + kTileU);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {  // the fp32 LSE of the split's rows
+            const int h = h0 + g * 4 + r;
+            if (wave == 0 && j == 0 && h < H) {
+                float* lp = part_lse + ((int64_t)b * H + h) * num_splits + split;
+                const float lv = empty ? -INFINITY : m_run[0][r] + __logf(l_run[0][r]);
+                if (FUSED) __hip_atomic_store(lp, lv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // write-through, like the rows
+                else *lp = lv;
+            }
+        }
+        mla_store_partial_rows(part_o, o_lds, o[0], inv, b, H, h0, split, num_splits, tid, wave, j, g);
+        CHITU_PROBE_MARK(13);
+        if (FUSED) {
+            // scratch: the second tile buffer's first bytes (the partial transpose above used the first buffer's)
+            mla_fused_tail(fuse, uvw, part_o, part_lse, b, H, h0, split, num_splits, b * (int)gridDim.z + hb, kv_lds + kTileU);
+        }
     }
 }
 
@@ -438,15 +472,6 @@ void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, 
 
 }  // namespace chitu
 
-// Dynamic LDS of a decode workgroup; the opt-in above 64 KB is set on every call (it is per device and cheap; a process-wide
-// "done" flag would leave the second GPU of a multi-device process without it).
-template <bool FUSED>
-static size_t mla_decode_lds_bytes() {
-    const size_t lds = 2 * chitu::kTileU + 16 * chitu::kPStride * 2 + 2 * 64 * sizeof(float) + chitu::kMaxTilesLds * sizeof(int);
-    (void)hipFuncSetAttribute((const void*)chitu::mla_decode_kernel<FUSED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return lds;
-}
-
 extern "C" int chitu_hip_mla_decode_workspace_bytes(int32_t batch, int32_t heads, int32_t num_splits,
                                                     int64_t* bytes) {
     if (!bytes || batch < 0 || heads < 1 || num_splits < 1) return CHITU_ERR_BAD_ARG;
@@ -467,19 +492,40 @@ extern "C" int chitu_hip_mla_decode(const void* q_nope, int64_t qn_stride_b, int
     if (int rc = mla_decode_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, heads, num_pages, page_size, table_stride,
                                        kv_lora_rank, rope_dim, num_splits, 1))
         return rc;
-    if (batch == 0) return CHITU_OK;
-    bf16_t* part_o = nullptr;
-    float* part_lse = nullptr;
-    if (num_splits > 1)
-        if (int rc = mla_decode_carve_workspace(workspace, workspace_bytes, batch, heads, num_splits, &part_o, &part_lse)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)num_splits, (unsigned)batch, (unsigned)((heads + 15) / 16));
-    hipLaunchKernelGGL(mla_decode_kernel<false>, grid, dim3(256), mla_decode_lds_bytes<false>(), st, (const bf16_t*)q_nope, qn_stride_b,
-                       qn_stride_h, (const bf16_t*)q_pe, qp_stride_b, qp_stride_h, (const bf16_t*)kv_cache,
-                       num_pages, (int)page_size, block_table, (int)table_stride, seqlens, softmax_scale,
-                       part_o, part_lse, (bf16_t*)out_bf16, (int)heads, (int)num_splits, MlaFuse{});
-    if (num_splits > 1 && out_bf16) launch_mla_merge(part_o, part_lse, (bf16_t*)out_bf16, (int64_t)batch * heads, (int)num_splits, st);
-    CHITU_RETURN_LAUNCH_STATUS();
+    return mla_decode_launch(mla_decode_kernel<1, false>, MlaLdsBf16::kBytes, (unsigned)((heads + 15) / 16), batch, batch, heads,
+                             num_splits, workspace, workspace_bytes, out_bf16, st,
+                             [&](auto kernel, dim3 grid, int lds, bf16_t* part_o, float* part_lse) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, (const bf16_t*)q_nope, MlaQStride<1>{qn_stride_b, qn_stride_h},
+                           (const bf16_t*)q_pe, MlaQStride<1>{qp_stride_b, qp_stride_h}, (const bf16_t*)kv_cache, num_pages,
+                           (int)page_size, block_table, (int)table_stride, seqlens, softmax_scale, part_o, part_lse,
+                           (bf16_t*)out_bf16, (int)heads, (int)num_splits, MlaFuse{}, MlaQLen<1>{});
+    });
+}
+
+extern "C" int chitu_hip_mla_decode_multi(const void* q_nope, int64_t qn_stride_b, int64_t qn_stride_t, int64_t qn_stride_h,
+                                          const void* q_pe, int64_t qp_stride_b, int64_t qp_stride_t, int64_t qp_stride_h,
+                                          const void* kv_cache, int64_t num_pages, int32_t page_size,
+                                          const int32_t* block_table, int32_t table_stride, const int32_t* seqlens,
+                                          float softmax_scale, void* out_bf16, int32_t batch, int32_t q_len, int32_t heads,
+                                          int32_t kv_lora_rank, int32_t rope_dim, int32_t num_splits, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+    using namespace chitu;
+    CHITU_REQUIRE(out_bf16 || num_splits > 1);  // no out: leave the split partials for a fused consumer
+    if (int rc = mla_decode_multi_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, q_len, heads, num_pages, page_size,
+                                             table_stride, kv_lora_rank, rope_dim, num_splits, qn_stride_b, qn_stride_t, qn_stride_h,
+                                             qp_stride_b, qp_stride_t, qp_stride_h))
+        return rc;
+    hipStream_t st = (hipStream_t)stream;
+    return mla_decode_launch(mla_decode_kernel<2, false>, MlaLdsBf16::kBytes, (unsigned)(((heads + 15) / 16) * ((q_len + 1) / 2)),
+                             batch * q_len, batch, heads, num_splits, workspace, workspace_bytes, out_bf16, st,
+                             [&](auto kernel, dim3 grid, int lds, bf16_t* part_o, float* part_lse) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, (const bf16_t*)q_nope,
+                           MlaQStride<2>{qn_stride_b, qn_stride_t, qn_stride_h}, (const bf16_t*)q_pe,
+                           MlaQStride<2>{qp_stride_b, qp_stride_t, qp_stride_h}, (const bf16_t*)kv_cache, num_pages, (int)page_size,
+                           block_table, (int)table_stride, seqlens, softmax_scale, part_o, part_lse, (bf16_t*)out_bf16, (int)heads,
+                           (int)num_splits, MlaFuse{}, MlaQLen<2>{(int)q_len});
+    });
 }
 
 extern "C" int chitu_hip_mla_decode_tickets_bytes(int64_t* bytes) {
@@ -504,18 +550,17 @@ extern "C" int chitu_hip_mla_decode_merge_uv_quant_fp8(
         return rc;
     const int hb = (heads + 15) / 16;
     if ((int64_t)batch * hb > kFuseMaxGroups) return CHITU_ERR_UNSUPPORTED;
-    if (batch == 0) return CHITU_OK;
-    bf16_t* part_o;
-    float* part_lse;
-    if (int rc = mla_decode_carve_workspace(workspace, workspace_bytes, batch, heads, num_splits, &part_o, &part_lse)) return rc;
     const MlaFuse fuse{(const fp8_t*)w_fp8, w_stride_h, scale, scale_offset, scale_stride_h, scale_stride_k, (fp8_t*)q_fp8, q_scales,
                        (int)tile_major, tickets};
-    const dim3 grid((unsigned)num_splits, (unsigned)batch, (unsigned)hb);
-    hipLaunchKernelGGL(mla_decode_kernel<true>, grid, dim3(256), mla_decode_lds_bytes<true>(), (hipStream_t)stream, (const bf16_t*)q_nope,
-                       qn_stride_b, qn_stride_h, (const bf16_t*)q_pe, qp_stride_b, qp_stride_h, (const bf16_t*)kv_cache, num_pages,
-                       (int)page_size, block_table, (int)table_stride, seqlens, softmax_scale, part_o, part_lse, (bf16_t*)nullptr,
-                       (int)heads, (int)num_splits, fuse);
-    CHITU_RETURN_LAUNCH_STATUS();
+    hipStream_t st = (hipStream_t)stream;
+    return mla_decode_launch(mla_decode_kernel<1, true>, MlaLdsBf16::kBytes, (unsigned)hb, batch, batch, heads, num_splits,
+                             workspace, workspace_bytes, /*out: the tail merges*/ nullptr, st,
+                             [&](auto kernel, dim3 grid, int lds, bf16_t* part_o, float* part_lse) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, (const bf16_t*)q_nope, MlaQStride<1>{qn_stride_b, qn_stride_h},
+                           (const bf16_t*)q_pe, MlaQStride<1>{qp_stride_b, qp_stride_h}, (const bf16_t*)kv_cache, num_pages,
+                           (int)page_size, block_table, (int)table_stride, seqlens, softmax_scale, part_o, part_lse, (bf16_t*)nullptr,
+                           (int)heads, (int)num_splits, fuse, MlaQLen<1>{});
+    });
 }
 
 CHITU_PROBE_READER(mla_decode)

@@ -1,7 +1,9 @@
-// What the MLA paged decode kernels share (mla_decode.hip: bf16 cache, mla_decode_kv_fp8.hip: fp8 latent cache): the bf16 tile
-// image and its fragment addressing, the tile step (QK^T, online softmax, P -> bf16, PV), the empty-split publication, the
-// epilogue and the host-side argument checks.  The two kernels differ in how a tile's bytes reach the image, and in nothing
-// behind that: the fp8 kernel's output is bit-identical to the bf16 kernel's on the dequantised cache because both run this text.
+// What the MLA paged decode kernels share (mla_decode.hip: bf16 cache, mla_decode_kv_fp8.hip: fp8 latent cache; each one kernel
+// template over kTok = 1 or 2 query tokens per workgroup): the bf16 tile image and its fragment addressing, the tile step (QK^T,
+// online softmax, P -> bf16, PV), the split range, the page lookup, Q's addressing, the LDS carve-up, the empty-split publication,
+// the epilogue, and the host side (argument checks, workspace, launch).  The two formats differ in how a tile's bytes reach the
+// image, and in nothing behind that: the fp8 kernel's output is bit-identical to the bf16 kernel's on the dequantised cache
+// because both run this text.
 #pragma once
 #include "common.h"
 
@@ -58,6 +60,114 @@ __device__ __forceinline__ void mla_q_frags(s16x8 (&qf)[18], const uint8_t* img,
     for (int kk = 0; kk < 18; ++kk)
         qf[kk] = *reinterpret_cast<const s16x8*>(img + j * kRowU + (kk >> 1) * 128 + (((g + 4 * (kk & 1)) ^ ksw0) << 4));
 }
+
+// ---- what a workgroup works on.  kTok = 1: one query token per sequence (q_len 1, row b); kTok = 2: q_len = T <= kMlaMultiMaxQ
+// tokens per sequence, two per workgroup.  Q's strides and the query length reach the kernels as structs templated on kTok: the
+// one-token forms hold no token stride and no T.
+constexpr int kMlaMultiMaxQ = 8;  // cache_manager.MAX_DECODE_Q
+template <int kTok>
+struct MlaQStride {
+    int64_t b, t, h;
+};
+template <>
+struct MlaQStride<1> {
+    int64_t b, h;
+};
+template <int kTok>
+struct MlaQLen {
+    int T;
+};
+template <>
+struct MlaQLen<1> {};
+template <int kTok>
+__device__ __forceinline__ int mla_q_len(const MlaQLen<kTok>& ql) {
+    if constexpr (kTok == 1) return 1;
+    else return ql.T;
+}
+
+// blockIdx.z -> (head block, the pair's tokens t0, t1); an odd T's last pair has one token (two == false, t1 == t0)
+struct MlaPair {
+    int hb, t0, t1;
+    bool two;
+};
+template <int kTok>
+__device__ __forceinline__ MlaPair mla_pair_of_block(int z, int T) {
+    if constexpr (kTok == 1) return MlaPair{z, 0, 0, false};
+    const int pairs = (T + 1) >> 1;
+    MlaPair p;
+    p.hb = z / pairs;
+    p.t0 = 2 * (z % pairs);
+    p.two = p.t0 + 1 < T;
+    p.t1 = p.two ? p.t0 + 1 : p.t0;
+    return p;
+}
+
+// Chunk c < 1152 of the Q block (16 heads x 576 = 72 chunks of 16 B per head) of query token t of sequence b; heads past H
+// re-read head H - 1
+template <int kTok>
+__device__ __forceinline__ const bf16_t* mla_q_chunk_src(const bf16_t* q_nope, const MlaQStride<kTok>& qn, const bf16_t* q_pe,
+                                                         const MlaQStride<kTok>& qp, int b, int t, int h0, int H, int c) {
+    const int row = c / 72, col = c % 72;
+    const int h = min(h0 + row, H - 1);
+    if constexpr (kTok == 1)
+        return col < 64 ? q_nope + b * qn.b + h * qn.h + col * 8 : q_pe + b * qp.b + h * qp.h + (col - 64) * 8;
+    else
+        return col < 64 ? q_nope + b * qn.b + t * qn.t + h * qn.h + col * 8 : q_pe + b * qp.b + t * qp.t + h * qp.h + (col - 64) * 8;
+}
+
+// The tiles [tile0, tile1) of split `split` of a sequence of L keys (32-bit unsigned quotients: the host bounds tiles x splits)
+struct MlaSplit {
+    int tile0, tile1;
+    bool pages_in_lds;  // the split's page ids fit the LDS list
+};
+__device__ __forceinline__ MlaSplit mla_split_range(int L, int split, int num_splits) {
+    const int n_tiles = (L + kTile - 1) / kTile;
+    MlaSplit sp;
+    sp.tile0 = (int)((unsigned)n_tiles * (unsigned)split / (unsigned)num_splits);
+    sp.tile1 = (int)((unsigned)n_tiles * (unsigned)(split + 1) / (unsigned)num_splits);
+    sp.pages_in_lds = (sp.tile1 - sp.tile0) <= kMaxTilesLds;
+    return sp;
+}
+
+// Where the rows of the tile that starts at token t0 lie, given its page id; row_bytes: 1152 (bf16) or 656 (fp8).  (The range test
+// is made on the 32-bit id, before it is widened: tested as a 64-bit value it compiles to 64-bit vector compares on the
+// seqlens -> table -> page -> request chain.)
+__device__ __forceinline__ const uint8_t* mla_page_src(const uint8_t* cache, int row_bytes, int64_t num_pages, int page_size,
+                                                       int page_id, int t0) {
+    const int64_t page = page_id >= 0 && page_id < num_pages ? page_id : 0;  // corrupt table: stay in bounds
+    return cache + (page * page_size + (t0 % page_size)) * (int64_t)row_bytes;
+}
+// ... of tile `tile` of the split: its page id from the LDS list (from_lds: the caller's rule for when that list may be read)
+// or from the table
+__device__ __forceinline__ const uint8_t* mla_tile_src(const uint8_t* cache, int row_bytes, int64_t num_pages, int page_size,
+                                                       const int32_t* tbl, int max_page_idx, const int* pages_lds, bool from_lds,
+                                                       int tile, int tile0) {
+    const int t0 = tile * kTile;
+    const int page_id = from_lds ? pages_lds[tile - tile0] : tbl[min(t0 / page_size, max_page_idx)];
+    return mla_page_src(cache, row_bytes, num_pages, page_size, page_id, t0);
+}
+// The LDS list: page ids of the split's tiles (none at one tile per split, the short-context shape: no table load, and no wait
+// of the compiler's for one -- which, counting in order, would also wait for the tile requested before)
+__device__ __forceinline__ void mla_fill_page_list(int* pages_lds, const int32_t* tbl, int max_page_idx, int page_size,
+                                                   const MlaSplit& sp, int tid) {
+    if (sp.pages_in_lds && sp.tile1 - sp.tile0 > 1) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+            if (tid + i * 256 < sp.tile1 - sp.tile0)
+                pages_lds[tid + i * 256] = tbl[min(((sp.tile0 + tid + i * 256) * kTile) / page_size, max_page_idx)];
+    }
+}
+
+// Dynamic LDS of a decode workgroup: kTiles bytes of tile images and staging (bf16: two images; fp8: one image and the staging
+// buffers), then P [16][kPStride] bf16, the softmax exchange red_max / red_sum [4][16] fp32 and the page list [kMaxTilesLds].
+// The kernels' pointers and the host's byte count both come from these offsets.  (Offsets, not pointer members, and the tokens'
+// state as plain arrays, not structs: either struct form changed the compiler's register allocation or its schedule of the PV
+// reads.)
+template <int kTiles>
+struct MlaLds {
+    static constexpr int kP = kTiles, kRedMax = kP + 16 * kPStride * 2, kRedSum = kRedMax + 64 * 4, kPages = kRedSum + 64 * 4;
+    static constexpr int kBytes = kPages + kMaxTilesLds * 4;
+};
 
 // One 64-token tile whose image is complete at `kv` and visible to the workgroup: the caller has waited, met and issued what
 // it issues.  p_lds [16][kPStride], red_max / red_sum [4][16]: free on entry, in use until the caller's next barrier.
@@ -186,7 +296,50 @@ __device__ __forceinline__ void mla_store_partial_rows(bf16_t* part_o, bf16_t* o
     }
 }
 
-// ---- host side of the three decode entries
+// ---- kTok = 2: everything above is used as it is -- a staged tile is multiplied once per token of the pair by mla_tile_step with
+// that token's own state, so a token's arithmetic and its order are the one-token kernels'.
+
+// What a query token keeps across the tiles -- its Q fragments qf[18] (the A operand), accumulators o[8] and running max / sum
+// m_run[4], l_run[4] -- lives in the kernels as arrays over the workgroup's kTok tokens.
+//
+// One staged tile, once per token of the pair: token k sees L_k keys, valid_k = min(64, L_k - tile * 64) of this tile's; a token
+// with none skips the step (the condition is workgroup-uniform: the barriers inside the step stay matched).  The exchange areas
+// are in use until a barrier, hence the one between the two steps.
+__device__ __forceinline__ void mla_pair_tile_steps(const uint8_t* kv, const MlaFrag& f, int tile, int L0, int L1, float scale,
+                                                    bf16_t* p_lds, float* red_max, float* red_sum, const s16x8 (&qf)[2][18],
+                                                    f32x4 (&o)[2][8], float (&m_run)[2][4], float (&l_run)[2][4], int wave, int j,
+                                                    int g) {
+    const int valid0 = min(kTile, L0 - tile * kTile), valid1 = min(kTile, L1 - tile * kTile);
+    if (valid0 > 0) mla_tile_step(kv, qf[0], f, valid0, scale, p_lds, red_max, red_sum, o[0], m_run[0], l_run[0], wave, j, g);
+    if (valid1 > 0) {
+        if (valid0 > 0) __syncthreads();
+        mla_tile_step(kv, qf[1], f, valid1, scale, p_lds, red_max, red_sum, o[1], m_run[1], l_run[1], wave, j, g);
+    }
+}
+
+// A token's epilogue, `row` = b * T + t: the single-token kernels' (1 / l_run, LSE = m_run + log l_run) where the token saw a
+// key in this split; where it saw none (l_run == 0), zero rows and LSE = -inf, what mla_publish_empty_split writes.
+__device__ __forceinline__ void mla_token_epilogue(const f32x4 (&o)[8], const float (&m_run)[4], const float (&l_run)[4], bf16_t* part_o,
+                                                   float* part_lse, bf16_t* out, bf16_t* o_lds, int row, int H, int h0, int split,
+                                                   int num_splits, int tid, int wave, int j, int g) {
+    float inv[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) inv[r] = l_run[r] > 0.f ? 1.0f / l_run[r] : 0.f;
+    if (num_splits == 1) {
+        mla_store_out_rows(out, o, inv, row, H, h0, wave, j, g);
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int h = h0 + g * 4 + r;
+        if (wave == 0 && j == 0 && h < H)
+            part_lse[((int64_t)row * H + h) * num_splits + split] = l_run[r] > 0.f ? m_run[r] + __logf(l_run[r]) : -INFINITY;
+    }
+    mla_store_partial_rows(part_o, o_lds, o, inv, row, H, h0, split, num_splits, tid, wave, j, g);
+}
+
+// ---- host side of the five decode entries (chitu_hip_mla_decode, _merge_uv_quant_fp8, _multi: mla_decode.hip; _kv_fp8, _multi_kv_fp8:
+// mla_decode_kv_fp8.hip)
 // Stage 2 (mla_decode.hip: a kernel is launched from the translation unit that defines it)
 void launch_mla_merge(const bf16_t* part_o, const float* part_lse, bf16_t* out, int64_t rows, int num_splits, hipStream_t st);
 
@@ -207,83 +360,13 @@ static inline int mla_decode_check_args(const void* q_nope, const void* q_pe, co
     return CHITU_OK;
 }
 // workspace (num_splits > 1, batch > 0): bf16 partial rows [batch, heads, splits, 512] | fp32 LSE [batch, heads, splits]
-static inline int mla_decode_carve_workspace(void* workspace, int64_t workspace_bytes, int32_t batch, int32_t heads, int32_t num_splits,
+static inline int mla_decode_carve_workspace(void* workspace, int64_t workspace_bytes, int32_t rows, int32_t heads, int32_t num_splits,
                                              bf16_t** part_o, float** part_lse) {
-    const int64_t need = (int64_t)batch * heads * num_splits * (kC * 2 + 4);
+    const int64_t need = (int64_t)rows * heads * num_splits * (kC * 2 + 4);
     CHITU_REQUIRE(workspace && workspace_bytes >= need);
     *part_o = (bf16_t*)workspace;
-    *part_lse = (float*)(*part_o + (int64_t)batch * heads * num_splits * kC);
+    *part_lse = (float*)(*part_o + (int64_t)rows * heads * num_splits * kC);
     return CHITU_OK;
-}
-
-// ---- the multi-token entries (mla_decode_multi.hip, mla_decode_multi_kv_fp8.hip): q_len = T <= kMlaMultiMaxQ query tokens per
-// sequence, two per workgroup.  Everything above is used as it is: a staged tile is multiplied once per token of the pair by
-// mla_tile_step with that token's own state, so a token's arithmetic and its order are the single-token kernels'.
-constexpr int kMlaMultiMaxQ = 8;  // cache_manager.MAX_DECODE_Q
-
-// blockIdx.z -> (head block, the pair's tokens t0, t1); an odd T's last pair has one token (two == false, t1 == t0)
-struct MlaPair {
-    int hb, t0, t1;
-    bool two;
-};
-__device__ __forceinline__ MlaPair mla_pair_of_block(int z, int T) {
-    const int pairs = (T + 1) >> 1;
-    MlaPair p;
-    p.hb = z / pairs;
-    p.t0 = 2 * (z % pairs);
-    p.two = p.t0 + 1 < T;
-    p.t1 = p.two ? p.t0 + 1 : p.t0;
-    return p;
-}
-
-// what one query token keeps across the tiles: its Q fragments (the A operand), accumulators and running max / sum
-struct MlaTokenState {
-    s16x8 qf[18];
-    f32x4 o[8];
-    float m_run[4], l_run[4];
-};
-__device__ __forceinline__ void mla_token_init(MlaTokenState& s) {
-#pragma unroll
-    for (int c = 0; c < 8; ++c) s.o[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        s.m_run[r] = -INFINITY;
-        s.l_run[r] = 0.f;
-    }
-}
-
-// One staged tile, once per token of the pair: token k sees L_k keys, valid_k = min(64, L_k - tile * 64) of this tile's; a token
-// with none skips the step (the condition is workgroup-uniform: the barriers inside the step stay matched).  The exchange areas
-// are in use until a barrier, hence the one between the two steps.
-__device__ __forceinline__ void mla_pair_tile_steps(const uint8_t* kv, const MlaFrag& f, int tile, int L0, int L1, float scale,
-                                                    bf16_t* p_lds, float* red_max, float* red_sum, MlaTokenState& s0,
-                                                    MlaTokenState& s1, int wave, int j, int g) {
-    const int valid0 = min(kTile, L0 - tile * kTile), valid1 = min(kTile, L1 - tile * kTile);
-    if (valid0 > 0) mla_tile_step(kv, s0.qf, f, valid0, scale, p_lds, red_max, red_sum, s0.o, s0.m_run, s0.l_run, wave, j, g);
-    if (valid1 > 0) {
-        if (valid0 > 0) __syncthreads();
-        mla_tile_step(kv, s1.qf, f, valid1, scale, p_lds, red_max, red_sum, s1.o, s1.m_run, s1.l_run, wave, j, g);
-    }
-}
-
-// A token's epilogue, `row` = b * T + t: the single-token kernels' (1 / l_run, LSE = m_run + log l_run) where the token saw a
-// key in this split; where it saw none (l_run == 0), zero rows and LSE = -inf, what mla_publish_empty_split writes.
-__device__ __forceinline__ void mla_token_epilogue(const MlaTokenState& s, bf16_t* part_o, float* part_lse, bf16_t* out, bf16_t* o_lds,
-                                                   int row, int H, int h0, int split, int num_splits, int tid, int wave, int j, int g) {
-    float inv[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) inv[r] = s.l_run[r] > 0.f ? 1.0f / s.l_run[r] : 0.f;
-    if (num_splits == 1) {
-        mla_store_out_rows(out, s.o, inv, row, H, h0, wave, j, g);
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int h = h0 + g * 4 + r;
-        if (wave == 0 && j == 0 && h < H)
-            part_lse[((int64_t)row * H + h) * num_splits + split] = s.l_run[r] > 0.f ? s.m_run[r] + __logf(s.l_run[r]) : -INFINITY;
-    }
-    mla_store_partial_rows(part_o, o_lds, s.o, inv, row, H, h0, split, num_splits, tid, wave, j, g);
 }
 
 // the multi-token entries' argument checks: their own BAD_ARG checks, then the shared ones
@@ -297,6 +380,26 @@ static inline int mla_decode_multi_check_args(const void* q_nope, const void* q_
     CHITU_REQUIRE(((qn_sb | qn_st | qn_sh | qp_sb | qp_st | qp_sh) & 7) == 0);  // 16-byte loads of q
     return mla_decode_check_args(q_nope, q_pe, kv_cache, block_table, seqlens, batch, heads, num_pages, page_size, table_stride,
                                  kv_lora_rank, rope_dim, num_splits, 1);
+}
+
+// What every entry does behind its argument checks: nothing at batch 0; the workspace carve (num_splits > 1); the opt-in above
+// 64 KB of dynamic LDS, set on every call (it is per device and cheap; a process-wide "done" flag would leave the second GPU of a
+// multi-device process without it); the launch on grid (num_splits, batch, grid_z) -- `launch(kernel, grid, lds_bytes, part_o,
+// part_lse)` is the entry's own hipLaunchKernelGGL, which adds the kernel's arguments -- and stage 2 over `rows` = batch * q_len
+// query rows where there is an `out` to merge into (no out: the split partials are left for a fused consumer).
+template <typename Kernel, typename Launch>
+static inline int mla_decode_launch(Kernel kernel, int lds_bytes, unsigned grid_z, int32_t rows, int32_t batch, int32_t heads,
+                                    int32_t num_splits, void* workspace, int64_t workspace_bytes, void* out_bf16, hipStream_t st,
+                                    Launch launch) {
+    if (batch == 0) return CHITU_OK;
+    bf16_t* part_o = nullptr;
+    float* part_lse = nullptr;
+    if (num_splits > 1)
+        if (int rc = mla_decode_carve_workspace(workspace, workspace_bytes, rows, heads, num_splits, &part_o, &part_lse)) return rc;
+    (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    launch(kernel, dim3((unsigned)num_splits, (unsigned)batch, grid_z), lds_bytes, part_o, part_lse);
+    if (num_splits > 1 && out_bf16) launch_mla_merge(part_o, part_lse, (bf16_t*)out_bf16, (int64_t)rows * heads, (int)num_splits, st);
+    CHITU_RETURN_LAUNCH_STATUS();
 }
 
 }  // namespace chitu

@@ -52,7 +52,8 @@ def test_no_compiler_wait_inside_the_dma_fed_loops(tmp_path, src, kernel):
 def test_asm_loads_of_mla_decode_are_untouched_until_their_wait(tmp_path):
     """mla_decode.hip requests seqlens and four page-table entries through inline-asm loads and waits for them in a LATER asm
     statement (so that they head the kernel); the compiler treats their outputs as defined at once.  Nothing may touch those
-    registers in between (check_flash_asm.audit_async_asm_loads reads the compiled ISA of both instantiations)."""
+    registers in between (check_flash_asm.audit_async_asm_loads reads the compiled ISA of the three instantiations: one token,
+    one token with the fused tail, two tokens)."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import check_flash_asm
 
@@ -62,4 +63,30 @@ def test_asm_loads_of_mla_decode_are_untouched_until_their_wait(tmp_path):
     res = subprocess.run(cmd, capture_output=True, text=True)
     assert res.returncode == 0, res.stderr
     seen, bad = check_flash_asm.audit_async_asm_loads(str(tmp_path / "k.s"), "mla_decode_kernel")
-    assert len(seen) == 2 and not bad, bad
+    assert len(seen) == 3 and not bad, bad
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_mla_decode_kernels_fit_the_register_file_without_scratch(tmp_path):
+    """The five MLA paged decode instantiations (mla_decode.hip: one token, one token with the fused tail, two tokens;
+    mla_decode_kv_fp8.hip: one and two tokens) hold two tokens' Q fragments, accumulators and state in registers.  Their launch
+    bound (256, 1) is one wave per SIMD, so up to the 512 unified registers the occupancy cannot change; above that, or with
+    scratch or spills, the kernel is a different kernel.  Read from the code-object metadata of the compiled ISA."""
+    import re
+
+    csrc = os.path.join(ROOT, "chitu_amd", "csrc")
+    found = {}
+    for src in ("mla_decode.hip", "mla_decode_kv_fp8.hip"):
+        out = tmp_path / (src + ".s")
+        cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-I" + os.path.join(ROOT, "include"), "-I" + csrc,
+               "-S", "--cuda-device-only", os.path.join(csrc, src), "-o", str(out)]
+        res = subprocess.run(cmd, capture_output=True, text=True)
+        assert res.returncode == 0, res.stderr
+        for blk in re.split(r"\n  - \.agpr_count:", out.read_text())[1:]:
+            name = re.search(r"\.name:\s*(\S+)", blk).group(1)
+            if re.search(r"mla_decode(_kv_fp8)?_kernel", name):
+                found[name] = {k: int(re.search(r"\." + k + r":\s*(\d+)", blk).group(1))
+                               for k in ("private_segment_fixed_size", "vgpr_spill_count", "vgpr_count")}
+    assert len(found) == 5, sorted(found)
+    for name, r in found.items():
+        assert r["private_segment_fixed_size"] == 0 and r["vgpr_spill_count"] == 0 and r["vgpr_count"] <= 512, (name, r)

@@ -1,5 +1,5 @@
-"""Multi-token MLA paged decode on the GPU (chitu_hip_mla_decode_multi / _kv_fp8, csrc/mla_decode_multi.hip, through
-HipAttnBackend.mla_decode_multi): the bit-identity table of the kernel's header against chitu_hip_mla_decode on the expanded
+"""Multi-token MLA paged decode on the GPU (chitu_hip_mla_decode_multi / _kv_fp8, the kTok = 2 kernels of csrc/mla_decode.hip and
+csrc/mla_decode_kv_fp8.hip, through HipAttnBackend.mla_decode_multi): the bit-identity table of the kernel's header against chitu_hip_mla_decode on the expanded
 problem, the attention bar and the counting construction where no bit claim is made, the causality probe, the fp8 entry
 against the bf16 entry on the dequantised cache, strided q and the argument errors.  Page size 64; wherever no key lives the
 caches hold NaN (tests/mla_multi_ref.py)."""

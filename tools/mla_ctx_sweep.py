@@ -4,6 +4,8 @@ python tools/mla_ctx_sweep.py [bs=16] -> JSON lines {ctx, splits, decode_us, mer
 16 local heads (TP=8 rank of R1), 64-token pages, random latent cache; each launch pair is captured 50x in a
 hipGraph and timed with events on the replay stream; kv bytes = bs * ctx * 576 * 2.
 
+--fused: also the one-launch form chitu_hip_mla_decode_merge_uv_quant_fp8 (bf16 cache only), 50 launches captured in a hipGraph,
+median of --repeats timed replays behind --warmup untimed ones, as fused_us (min ... max beside it).
 --kv-format fp8: the same sweep over the fp8 latent cache (chitu_hip_mla_decode_kv_fp8; kv bytes = bs * ctx * 656).
 --kv-format ab [--bs 1 16 32] [--out profiles/mla_kv_fp8_ctx_sweep.json]: both formats in ONE process -- the decode (+ merge)
 launches of the bf16 and the fp8 cache, each captured 20x in a hipGraph, the two graphs replayed alternately; medians with
@@ -31,6 +33,7 @@ sys.path.insert(0, ROOT)
 ap = argparse.ArgumentParser()
 ap.add_argument("bs_pos", nargs="?", type=int, default=None, help="batch size (the original positional form)")
 ap.add_argument("--kv-format", choices=("bf16", "fp8", "ab"), default="bf16")
+ap.add_argument("--fused", action="store_true", help="default mode, bf16 cache: also time the fused decode + merge + W_UV + quant launch")
 ap.add_argument("--bs", type=int, nargs="*", default=None)
 ap.add_argument("--ctx", type=int, nargs="*", default=None, help="contexts (default 1024 4096 8192 32768; with --multi 1024 8192)")
 ap.add_argument("--repeats", type=int, default=15)
@@ -267,6 +270,15 @@ def sweep_one(bs, fmt):
                "frac_of_8TBs": round(kv / res["decode"] / 1e6 / 8, 3)}
         if fmt == "fp8":
             row["kv_format"] = "fp8"
+        elif a.fused:
+            def fused():
+                return be.mla_decode_merge_uv_quant(q_nope, q_pe, cache, lens, table, 0.1, w_uv, sc, 4, 8, 1)
+
+            if fused() is None:
+                row["fused_us"] = None  # the shape takes the two-launch form (one split)
+            else:
+                us = alternate({"fused": capture(fused, 50)}, 50)["fused"]
+                row.update({"fused_us": round(statistics.median(us), 2), "fused_min_us": round(min(us), 2), "fused_max_us": round(max(us), 2)})
         print(json.dumps(row), flush=True)
         del cache
         torch.cuda.empty_cache()
