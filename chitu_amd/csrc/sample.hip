@@ -20,6 +20,9 @@
 // torch.multinomial on the masked probabilities, and reproducible given u.
 //
 // One workgroup (1024 threads) per row; rows are independent.
+//
+// chitu_hip_speculative_verify (below, new: no reference counterpart) is the same row with a draft token: the passes are
+// shared, and the acceptance test sits between the kept prefix and the draw.
 #include "common.h"
 
 namespace chitu {
@@ -150,6 +153,8 @@ struct SampleShared {
     uint32_t wave_u32[kSampleWaves];
     uint64_t seg_strict[kSampleWaves];
     uint32_t seg_ties[kSampleWaves];
+    uint64_t seg_draft[kSampleWaves];       // chitu_hip_speculative_verify: the draft's entry, found by the segment pass
+    uint32_t seg_ties_below[kSampleWaves];  // and the ties at tau below the draft's index
     // boundary bin of the current level
     int b_found;
     uint32_t b_bin, b_cexcl, b_cnt;
@@ -337,13 +342,94 @@ __device__ __forceinline__ void bitonic_sort_lds(uint64_t* a, int n) {
     }
 }
 
+// The integer position in [0, s) that a uniform u in [0, 1) selects, s > 0 (oracle/sampling.py::sample_fixed_point).
+__device__ __forceinline__ uint64_t sample_target(float u, uint64_t s) {
+    const double t = (double)__builtin_fminf(__builtin_fmaxf(u, 0.f), 1.f) * (double)s;
+    uint64_t target = t >= (double)s ? s - 1 : (uint64_t)t;
+    if (target >= s) target = s - 1;
+    return target;
+}
+
+// One row of chitu_hip_sample, or (VERIFY) of chitu_hip_speculative_verify: the sample row with a draft.  Both kernels run
+// the passes below on it; what VERIFY adds is compiled out of the sample kernel (if constexpr).
+struct SampleRow {
+    const void* row;
+    int vocab;
+    bool vec;
+    float temperature;
+    int probs_mode;
+    int top_k;
+    float top_p;
+    float u;  // the draw's uniform (VERIFY: u_alt, which draws the replacement / bonus token)
+    int row_id;
+    int64_t arg_max;
+    float m;  // the row maximum of x
+    int64_t* token_out;  // this row's slot (VERIFY: the token, bit 32 set when the draft was accepted)
+    int32_t* n_kept_out;
+    float* kept_mass_out;
+    // VERIFY only
+    int draft;    // the proposed token; < 0: none (the bonus row), the row is a plain draw
+    float u_acc;  // accepted iff target(u_acc, S) < w_draft
+    int32_t* accepted_out;
+    int64_t* row_token_out;
+};
+
+constexpr int64_t kVerifyAcceptedBit = (int64_t)1 << 32;  // tokens are < 2^31
+
+// Called by one thread of the row's workgroup.
+template <bool VERIFY>
+__device__ __forceinline__ void sample_emit(const SampleRow& r, int64_t token, bool accepted) {
+    if constexpr (VERIFY) {
+        *r.token_out = accepted ? (token | kVerifyAcceptedBit) : token;
+        if (r.accepted_out) r.accepted_out[r.row_id] = accepted ? 1 : 0;
+        if (r.row_token_out) r.row_token_out[r.row_id] = token;
+    } else {
+        *r.token_out = token;
+    }
+}
+
+// Pass 0: the row maximum of x and its (lowest) index -> r.m, r.arg_max.  Must be called by the whole workgroup.
+template <int DT>
+__device__ __forceinline__ void sample_row_max(SampleShared& sh, SampleRow& r) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float temperature = r.temperature;
+    const int probs_mode = r.probs_mode;
+    uint64_t best = 0;
+    for_each_quad<DT, kSampleUnroll>(r.row, r.vocab, r.vec, [&](int i0, const float (&v)[4], int n) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k < n) {
+                const uint64_t key = ((uint64_t)ordered_key(sample_x(v[k], temperature, probs_mode)) << 32) |
+                                     (uint32_t)(0xffffffffu - (uint32_t)(i0 + k));
+                best = key > best ? key : best;
+            }
+        }
+    });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const uint64_t o = shfl_xor_u64(best, off);
+        best = o > best ? o : best;
+    }
+    if (lane == 0) sh.wave_u64[wave] = best;
+    __syncthreads();
+    best = sh.wave_u64[0];
+#pragma unroll
+    for (int w = 1; w < kSampleWaves; ++w) best = sh.wave_u64[w] > best ? sh.wave_u64[w] : best;
+    __syncthreads();  // wave_u64 is reused below
+    r.arg_max = (int64_t)(0xffffffffu - (uint32_t)best);
+    r.m = ordered_key_inv((uint32_t)(best >> 32));
+}
+
 // Returns true when the token (and the optional statistics) have been written; false = not applicable,
 // nothing written, the caller runs the radix descent.  Must be called by the whole workgroup.
-template <int DT>
-__device__ __forceinline__ bool sample_candidates(SampleShared& sh, const void* row, int vocab, bool vec, float temperature,
-                                                  float m, int probs_mode, int top_k, float top_p, float u, int row_id,
-                                                  int64_t arg_max, int64_t* out_tokens, int32_t* n_kept_out,
-                                                  float* kept_mass_out) {
+// VERIFY: membership and weight of the draft come from the sorted list; a rejected draft's entry is
+// left out of the second sort, so the inverse CDF runs over the kept set without it.
+template <int DT, bool VERIFY>
+__device__ __forceinline__ bool sample_candidates(SampleShared& sh, const SampleRow& r) {
+    const void* row = r.row;
+    const int vocab = r.vocab, probs_mode = r.probs_mode, top_k = r.top_k;
+    const bool vec = r.vec;
+    const float temperature = r.temperature, m = r.m, top_p = r.top_p;
     const int tid = threadIdx.x, lane = tid & 63;
     uint64_t* arr = sh.sum;  // the histogram's sum array doubles as the sort buffer (kCandCap == kSampleBins)
     // ---- pass 1: Z and the five threshold counts (21 bits each: vocab < 2^21 per the entry point)
@@ -421,92 +507,57 @@ __device__ __forceinline__ bool sample_candidates(SampleShared& sh, const void* 
     const bool sufficient = n_kept < n_cand || (uint32_t)n_cand >= k_eff || s_cand > p_rem || n_cand == vocab;
     if (!sufficient) return false;
     if (tid == 0) {
-        if (n_kept_out) n_kept_out[row_id] = n_kept;
-        if (kept_mass_out) kept_mass_out[row_id] = (float)((double)s_kept / (double)z);
+        if (r.n_kept_out) r.n_kept_out[r.row_id] = n_kept;
+        if (r.kept_mass_out) r.kept_mass_out[r.row_id] = (float)((double)s_kept / (double)z);
     }
     if (s_kept == 0) {
-        if (tid == 0) out_tokens[row_id] = arg_max;
+        if (tid == 0) sample_emit<VERIFY>(r, r.arg_max, VERIFY && (int64_t)r.draft == r.arg_max);
         return true;
     }
-    uint64_t target;
-    {
-        const double t = (double)__builtin_fminf(__builtin_fmaxf(u, 0.f), 1.f) * (double)s_kept;
-        target = t >= (double)s_kept ? s_kept - 1 : (uint64_t)t;
-        if (target >= s_kept) target = s_kept - 1;
+    uint64_t s_draw = s_kept;  // the mass the token is drawn from
+    int n_draw = n_kept;
+    bool in_draw = kept;
+    if constexpr (VERIFY) {
+        if (r.draft >= 0) {  // workgroup-uniform
+            const bool is_draft = kept && my_idx == (uint32_t)r.draft;
+            const uint64_t w_d = block_sum_u64(sh, is_draft ? w : 0ull);  // a kept candidate's weight is > 0: 0 = not kept
+            if (sample_target(r.u_acc, s_kept) < w_d) {  // probability w_d / S; w_d == S always accepts
+                if (tid == 0) sample_emit<VERIFY>(r, (int64_t)r.draft, true);
+                return true;
+            }
+            s_draw -= w_d;
+            n_draw -= w_d ? 1 : 0;
+            in_draw = kept && !is_draft;
+        }
     }
+    const uint64_t target = sample_target(r.u, s_draw);
     // ---- inverse CDF over the kept entries in INDEX order: sort them by index, scan, pick
     __syncthreads();
-    if (tid < npow) arr[tid] = kept ? (((uint64_t)my_idx << 32) | my_key) : ~0ull;
+    if (tid < npow) arr[tid] = in_draw ? (((uint64_t)my_idx << 32) | my_key) : ~0ull;
     __syncthreads();
     bitonic_sort_lds<false>(arr, npow);
-    const uint64_t ent = tid < n_kept ? arr[tid] : 0ull;
-    const uint64_t w2 = tid < n_kept ? sample_fix(__uint_as_float((uint32_t)ent)) : 0ull;
+    const uint64_t ent = tid < n_draw ? arr[tid] : 0ull;
+    const uint64_t w2 = tid < n_draw ? sample_fix(__uint_as_float((uint32_t)ent)) : 0ull;
     uint64_t unused_total;
     const uint64_t excl2 = block_excl_scan_u64(sh, w2, unused_total);
-    if (tid < n_kept && excl2 <= target && target < excl2 + w2) out_tokens[row_id] = (int64_t)(ent >> 32);
+    if (tid < n_draw && excl2 <= target && target < excl2 + w2) sample_emit<VERIFY>(r, (int64_t)(ent >> 32), false);
     return true;
 }
 
+// The kept prefix of a row from the radix descent: the kept set is {key > tau} plus the first c_keep ties at tau in index
+// order, every tie weighs e_tau, the kept mass is s_kept.  (keep_all: tau = 0, e_tau = 0, c_keep = all.)
+struct SampleCut {
+    uint32_t tau, c_keep;
+    uint64_t e_tau, s_kept;
+};
+
+// Radix descent for (tau, c_keep); writes the optional statistics.  Must be called by the whole workgroup.
 template <int DT>
-__global__ __launch_bounds__(kSampleThreads) void sample_kernel(
-    const void* __restrict__ logits, int64_t row_stride, int vocab, const float* __restrict__ temperatures,
-    const int32_t* __restrict__ top_ks, const float* __restrict__ top_ps, const float* __restrict__ uniforms,
-    int probs_mode, int64_t* __restrict__ out_tokens, int32_t* __restrict__ n_kept_out,
-    float* __restrict__ kept_mass_out, int use_candidates) {
-    __shared__ SampleShared sh;
-    const int row_id = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int elem = DT == 2 ? 4 : 2;
-    const char* row = reinterpret_cast<const char*>(logits) + (int64_t)row_id * row_stride * elem;
-    const bool vec = (reinterpret_cast<uintptr_t>(row) & (uintptr_t)(4 * elem - 1)) == 0;
-    const bool greedy_all = top_ks == nullptr;
-    const int top_k = greedy_all ? 1 : top_ks[row_id];
-    const float temperature = (greedy_all || probs_mode) ? 1.0f : temperatures[row_id];
-
-    // ---- pass 0: row maximum and its (lowest) index
-    uint64_t best = 0;
-    for_each_quad<DT, kSampleUnroll>(row, vocab, vec, [&](int i0, const float (&v)[4], int n) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (k < n) {
-                const uint64_t key = ((uint64_t)ordered_key(sample_x(v[k], temperature, probs_mode)) << 32) |
-                                     (uint32_t)(0xffffffffu - (uint32_t)(i0 + k));
-                best = key > best ? key : best;
-            }
-        }
-    });
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint64_t o = shfl_xor_u64(best, off);
-        best = o > best ? o : best;
-    }
-    if (lane == 0) sh.wave_u64[wave] = best;
-    __syncthreads();
-    best = sh.wave_u64[0];
-#pragma unroll
-    for (int w = 1; w < kSampleWaves; ++w) best = sh.wave_u64[w] > best ? sh.wave_u64[w] : best;
-    __syncthreads();  // wave_u64 is reused below
-    const int64_t arg_max = (int64_t)(0xffffffffu - (uint32_t)best);
-    const float m = ordered_key_inv((uint32_t)(best >> 32));
-    if (top_k == 1) {  // greedy row (executor.py:103-104; a top_k of 1 keeps only the first sorted entry)
-        if (tid == 0) {
-            out_tokens[row_id] = arg_max;
-            if (n_kept_out) n_kept_out[row_id] = 1;
-            if (kept_mass_out) kept_mass_out[row_id] = 0.f;
-        }
-        return;
-    }
-    const float top_p = top_ps[row_id];
-    const float u = uniforms[row_id];
-
-    // ---- short candidate list first (peaked rows); the radix descent below is the general path
-    if (use_candidates && vocab < (1 << 21) &&
-        sample_candidates<DT>(sh, row, vocab, vec, temperature, m, probs_mode, top_k, top_p, u, row_id, arg_max,
-                              out_tokens, n_kept_out, kept_mass_out))
-        return;
-    __syncthreads();  // the candidate path's LDS (sh.sum, counters) is about to be reused
-
-    // ---- radix descent for (tau, c_keep)
+__device__ __forceinline__ SampleCut sample_radix_cut(SampleShared& sh, const SampleRow& r) {
+    const void* row = r.row;
+    const int vocab = r.vocab, probs_mode = r.probs_mode, top_k = r.top_k;
+    const bool vec = r.vec;
+    const float temperature = r.temperature, m = r.m, top_p = r.top_p;
     uint32_t k_rem = top_k <= 0 ? 0xffffffffu : (uint32_t)top_k;  // <= 0: no top-k limit
     uint64_t p_rem = 0;
     uint32_t tau = 0, c_above = 0, c_keep = 0xffffffffu;
@@ -544,88 +595,78 @@ __global__ __launch_bounds__(kSampleThreads) void sample_kernel(
         c_keep = (uint32_t)(c_p < k_rem ? c_p : k_rem);
     }
     const uint64_t s_kept = keep_all ? z_total : s_above + (uint64_t)c_keep * e_tau;
-    if (tid == 0) {
-        if (n_kept_out) n_kept_out[row_id] = keep_all ? vocab : (int32_t)(c_above + c_keep);
-        if (kept_mass_out) kept_mass_out[row_id] = z_total ? (float)((double)s_kept / (double)z_total) : 0.f;
+    if (threadIdx.x == 0) {
+        if (r.n_kept_out) r.n_kept_out[r.row_id] = keep_all ? vocab : (int32_t)(c_above + c_keep);
+        if (r.kept_mass_out) r.kept_mass_out[r.row_id] = z_total ? (float)((double)s_kept / (double)z_total) : 0.f;
     }
-    if (s_kept == 0) {  // no positive weight at all (NaN row / all-zero probabilities)
-        if (tid == 0) out_tokens[row_id] = arg_max;
-        return;
-    }
-    uint64_t target;
-    {
-        const double t = (double)__builtin_fminf(__builtin_fmaxf(u, 0.f), 1.f) * (double)s_kept;
-        target = t >= (double)s_kept ? s_kept - 1 : (uint64_t)t;
-        if (target >= s_kept) target = s_kept - 1;
-    }
+    return SampleCut{tau, c_keep, e_tau, s_kept};
+}
 
-    // ---- inverse CDF in index order.  Pass A: kept mass and tie count of each wave's contiguous
-    // segment; then the one wave whose segment holds `target` rescans it with prefix sums.
-    const int seg_len = ((vocab + kSampleWaves - 1) / kSampleWaves + 255) / 256 * 256;
-    const int seg_begin = min(wave * seg_len, vocab), seg_end = min(seg_begin + seg_len, vocab);
-    {
-        uint64_t strict = 0;
-        uint32_t ties = 0;
-        for (int base = seg_begin; base < seg_end; base += 256) {
-            const int i0 = base + lane * 4;
-            if (i0 < seg_end) {
-                float v[4];
-                const int n = load4<DT>(row, i0, vocab, vec, v);
+// Segment pass: kept strict mass and tie count of each wave's contiguous segment -> sh.seg_strict / seg_ties.
+// VERIFY: also, per segment, the ties at tau with an index below the draft (summed: the draft's rank among the ties)
+// and the draft's own entry -- its weight if it is above tau, or that it is a tie -> sh.seg_ties_below / seg_draft.
+constexpr uint64_t kDraftIsTie = 1ull << 62;  // weights are <= 2^40
+template <int DT, bool VERIFY>
+__device__ __forceinline__ void sample_segment_pass(SampleShared& sh, const SampleRow& r, const SampleCut& cut, int seg_begin,
+                                                    int seg_end) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t tau = cut.tau;
+    uint64_t strict = 0, draft_entry = 0;
+    uint32_t ties = 0, ties_below = 0;
+    for (int base = seg_begin; base < seg_end; base += 256) {
+        const int i0 = base + lane * 4;
+        if (i0 < seg_end) {
+            float v[4];
+            const int n = load4<DT>(r.row, i0, r.vocab, r.vec, v);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float e = sample_e(sample_x(v[k], temperature, probs_mode), m, probs_mode);
-                    const uint32_t key = __float_as_uint(e);
-                    if (k < n) {
-                        if (key > tau) strict += sample_fix(e);
-                        ties += key == tau ? 1u : 0u;
+            for (int k = 0; k < 4; ++k) {
+                const float e = sample_e(sample_x(v[k], r.temperature, r.probs_mode), r.m, r.probs_mode);
+                const uint32_t key = __float_as_uint(e);
+                if (k < n) {
+                    if (key > tau) strict += sample_fix(e);
+                    ties += key == tau ? 1u : 0u;
+                    if constexpr (VERIFY) {
+                        ties_below += (key == tau && i0 + k < r.draft) ? 1u : 0u;
+                        if (i0 + k == r.draft) draft_entry = key > tau ? sample_fix(e) : (key == tau ? kDraftIsTie : 0ull);
                     }
                 }
             }
         }
-        strict = wave_sum_u64(strict);
-        ties = (uint32_t)wave_sum_u64((uint64_t)ties);
-        if (lane == 0) {
-            sh.seg_strict[wave] = strict;
-            sh.seg_ties[wave] = ties;
+    }
+    strict = wave_sum_u64(strict);
+    ties = (uint32_t)wave_sum_u64((uint64_t)ties);
+    if constexpr (VERIFY) {
+        draft_entry = wave_sum_u64(draft_entry);  // one lane of one wave at the most holds the draft
+        ties_below = (uint32_t)wave_sum_u64((uint64_t)ties_below);
+    }
+    if (lane == 0) {
+        sh.seg_strict[wave] = strict;
+        sh.seg_ties[wave] = ties;
+        if constexpr (VERIFY) {
+            sh.seg_draft[wave] = draft_entry;
+            sh.seg_ties_below[wave] = ties_below;
         }
     }
-    __syncthreads();
-    int wsel = -1;
-    uint64_t run = 0;        // kept mass before the selected segment
-    uint32_t ties_run = 0;   // ties before it
-    {
-        uint64_t cum = 0;
-        uint32_t tb = 0;
-#pragma unroll
-        for (int w = 0; w < kSampleWaves; ++w) {
-            const uint32_t st = sh.seg_ties[w];
-            const uint64_t left = (uint64_t)c_keep > (uint64_t)tb ? (uint64_t)c_keep - tb : 0ull;
-            const uint64_t kt = left < st ? left : (uint64_t)st;
-            const uint64_t s = sh.seg_strict[w] + kt * e_tau;
-            if (wsel < 0 && target < cum + s) {
-                wsel = w;
-                run = cum;
-                ties_run = tb;
-            }
-            cum += s;
-            tb += st;
-        }
-    }
-    if (wsel < 0) {  // unreachable (the segment sums add up to s_kept); keep the launch well-defined
-        if (tid == 0) out_tokens[row_id] = arg_max;
-        return;
-    }
-    if (wave != wsel) return;
+}
+
+// Rescan: the one wave whose segment holds `target` walks it with prefix sums and emits the token.  `run` / `ties_run`:
+// kept mass / ties before the segment.  VERIFY: the rejected draft's index weighs nothing.  Called by that wave alone.
+template <int DT, bool VERIFY>
+__device__ __forceinline__ void sample_rescan(const SampleRow& r, const SampleCut& cut, int seg_begin, int seg_end, uint64_t run,
+                                              uint32_t ties_run, uint64_t target) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t tau = cut.tau, c_keep = cut.c_keep;
+    const uint64_t e_tau = cut.e_tau;
     for (int base = seg_begin; base < seg_end; base += 256) {
         const int i0 = base + lane * 4;
         float v[4];
-        const int n = i0 < seg_end ? load4<DT>(row, i0, vocab, vec, v) : 0;
+        const int n = i0 < seg_end ? load4<DT>(r.row, i0, r.vocab, r.vec, v) : 0;
         uint64_t w4[4];
         bool tie4[4];
         uint32_t t_l = 0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            const float e = sample_e(sample_x(v[k], temperature, probs_mode), m, probs_mode);
+            const float e = sample_e(sample_x(v[k], r.temperature, r.probs_mode), r.m, r.probs_mode);
             const uint32_t key = __float_as_uint(e);
             tie4[k] = k < n && key == tau;
             w4[k] = (k < n && key > tau) ? sample_fix(e) : 0ull;
@@ -645,6 +686,9 @@ __global__ __launch_bounds__(kSampleThreads) void sample_kernel(
             if (tie4[k]) {
                 if (rank < c_keep) w4[k] = e_tau;
                 ++rank;
+            }
+            if constexpr (VERIFY) {
+                if (i0 + k == r.draft) w4[k] = 0ull;
             }
             s_l += w4[k];
         }
@@ -669,7 +713,7 @@ __global__ __launch_bounds__(kSampleThreads) void sample_kernel(
                         done = true;
                     }
                 }
-                out_tokens[row_id] = (int64_t)(i0 + pick);
+                sample_emit<VERIFY>(r, (int64_t)(i0 + pick), false);
             }
             return;
         }
@@ -677,7 +721,184 @@ __global__ __launch_bounds__(kSampleThreads) void sample_kernel(
                           (uint32_t)__shfl((int)(uint32_t)s_incl, 63, 64));
         ties_run += (uint32_t)__shfl((int)t_incl, 63, 64);
     }
-    if (lane == 0) out_tokens[row_id] = arg_max;  // unreachable, see above
+    if (lane == 0) sample_emit<VERIFY>(r, r.arg_max, false);  // unreachable: the segment sums add up to the drawn mass
+}
+
+// Everything after pass 0 for a row that is not greedy.  Must be called by the whole workgroup.
+template <int DT, bool VERIFY>
+__device__ __forceinline__ void sample_row_draw(SampleShared& sh, const SampleRow& r, int use_candidates) {
+    const int tid = threadIdx.x, wave = tid >> 6;
+    // ---- short candidate list first (peaked rows); the radix descent below is the general path
+    if (use_candidates && r.vocab < (1 << 21) && sample_candidates<DT, VERIFY>(sh, r)) return;
+    __syncthreads();  // the candidate path's LDS (sh.sum, counters) is about to be reused
+
+    const SampleCut cut = sample_radix_cut<DT>(sh, r);
+    if (cut.s_kept == 0) {  // no positive weight at all (NaN row / all-zero probabilities)
+        if (tid == 0) sample_emit<VERIFY>(r, r.arg_max, VERIFY && (int64_t)r.draft == r.arg_max);
+        return;
+    }
+    uint64_t target = 0;
+    if constexpr (!VERIFY) target = sample_target(r.u, cut.s_kept);
+
+    // ---- inverse CDF in index order.  Segment pass: kept mass and tie count of each wave's contiguous
+    // segment; then the one wave whose segment holds `target` rescans it with prefix sums.
+    const int seg_len = ((r.vocab + kSampleWaves - 1) / kSampleWaves + 255) / 256 * 256;
+    const int seg_begin = min(wave * seg_len, r.vocab), seg_end = min(seg_begin + seg_len, r.vocab);
+    sample_segment_pass<DT, VERIFY>(sh, r, cut, seg_begin, seg_end);
+    __syncthreads();
+    uint64_t w_d = 0;  // VERIFY: the rejected draft's kept weight, which its segment loses
+    int draft_wave = -1;
+    if constexpr (VERIFY) {
+        if (r.draft >= 0) {  // workgroup-uniform
+            uint64_t entry = 0;
+            uint32_t rank = 0;
+#pragma unroll
+            for (int w = 0; w < kSampleWaves; ++w) {
+                entry += sh.seg_draft[w];
+                rank += sh.seg_ties_below[w];
+            }
+            // a tie at tau is kept iff its rank among the ties in index order is below c_keep, as in the draw
+            w_d = (entry & kDraftIsTie) ? (rank < cut.c_keep ? cut.e_tau : 0ull) : entry;
+            if (sample_target(r.u_acc, cut.s_kept) < w_d) {  // probability w_d / S; w_d == S always accepts
+                if (tid == 0) sample_emit<VERIFY>(r, (int64_t)r.draft, true);
+                return;
+            }
+            draft_wave = r.draft / seg_len;
+        }
+        target = sample_target(r.u, cut.s_kept - w_d);
+    }
+    int wsel = -1;
+    uint64_t run = 0;        // kept mass before the selected segment
+    uint32_t ties_run = 0;   // ties before it
+    {
+        uint64_t cum = 0;
+        uint32_t tb = 0;
+#pragma unroll
+        for (int w = 0; w < kSampleWaves; ++w) {
+            const uint32_t st = sh.seg_ties[w];
+            const uint64_t left = (uint64_t)cut.c_keep > (uint64_t)tb ? (uint64_t)cut.c_keep - tb : 0ull;
+            const uint64_t kt = left < st ? left : (uint64_t)st;
+            uint64_t s = sh.seg_strict[w] + kt * cut.e_tau;
+            if constexpr (VERIFY) {
+                if (w == draft_wave) s -= w_d;
+            }
+            if (wsel < 0 && target < cum + s) {
+                wsel = w;
+                run = cum;
+                ties_run = tb;
+            }
+            cum += s;
+            tb += st;
+        }
+    }
+    if (wsel < 0) {  // unreachable (the segment sums add up to the drawn mass); keep the launch well-defined
+        if (tid == 0) sample_emit<VERIFY>(r, r.arg_max, false);
+        return;
+    }
+    if (wave != wsel) return;
+    sample_rescan<DT, VERIFY>(r, cut, seg_begin, seg_end, run, ties_run, target);
+}
+
+template <int DT>
+__global__ __launch_bounds__(kSampleThreads) void sample_kernel(
+    const void* __restrict__ logits, int64_t row_stride, int vocab, const float* __restrict__ temperatures,
+    const int32_t* __restrict__ top_ks, const float* __restrict__ top_ps, const float* __restrict__ uniforms,
+    int probs_mode, int64_t* __restrict__ out_tokens, int32_t* __restrict__ n_kept_out,
+    float* __restrict__ kept_mass_out, int use_candidates) {
+    __shared__ SampleShared sh;
+    const int row_id = blockIdx.x;
+    const int elem = DT == 2 ? 4 : 2;
+    const bool greedy_all = top_ks == nullptr;
+    SampleRow r = {};
+    r.row = reinterpret_cast<const char*>(logits) + (int64_t)row_id * row_stride * elem;
+    r.vocab = vocab;
+    r.vec = (reinterpret_cast<uintptr_t>(r.row) & (uintptr_t)(4 * elem - 1)) == 0;
+    r.top_k = greedy_all ? 1 : top_ks[row_id];
+    r.temperature = (greedy_all || probs_mode) ? 1.0f : temperatures[row_id];
+    r.probs_mode = probs_mode;
+    r.row_id = row_id;
+    r.token_out = out_tokens + row_id;
+    r.n_kept_out = n_kept_out;
+    r.kept_mass_out = kept_mass_out;
+    sample_row_max<DT>(sh, r);
+    if (r.top_k == 1) {  // greedy row (executor.py:103-104; a top_k of 1 keeps only the first sorted entry)
+        if (threadIdx.x == 0) {
+            out_tokens[row_id] = r.arg_max;
+            if (n_kept_out) n_kept_out[row_id] = 1;
+            if (kept_mass_out) kept_mass_out[row_id] = 0.f;
+        }
+        return;
+    }
+    r.top_p = top_ps[row_id];
+    r.u = uniforms[row_id];
+    sample_row_draw<DT, false>(sh, r, use_candidates);
+}
+
+// ---------------------------------------------------------------- speculative decoding: draft verification
+// Row stage of chitu_hip_speculative_verify (new: no reference counterpart): row (b, t) of T rows per sequence is the
+// sample row with the deterministic draft drafts[row] for its token.  The draft distribution is a point mass, so
+// rejection sampling against the row's distribution p is: accept d with probability p(d) = w_d / S (in the sampler's
+// integers: target(u_acc, S) < w_d), otherwise draw from p without d, renormalised (the inverse CDF over K \ {d} at
+// target(u_alt, S - w_d)).  Lossless: P(emit d) = p(d), and P(emit x != d) = (1 - p(d)) * p(x) / (1 - p(d)) = p(x).
+// Greedy (top_k == 1) and degenerate (S == 0) rows accept iff d == argmax and emit the arg-max; a row without a draft
+// (d < 0, the bonus row) is chitu_hip_sample's row for u_alt.  The specification is tests/spec_verify_ref.py.
+// The row writes its token into out[b, 1 + t], with kVerifyAcceptedBit set when the draft was accepted; the sequence
+// stage (next launch) turns that into the result.
+template <int DT>
+__global__ __launch_bounds__(kSampleThreads) void verify_rows_kernel(
+    const void* __restrict__ logits, int64_t row_stride, int vocab, const float* __restrict__ temperatures,
+    const int32_t* __restrict__ top_ks, const float* __restrict__ top_ps, const int32_t* __restrict__ drafts,
+    const float* __restrict__ uniforms, int q_len, int probs_mode, int64_t* __restrict__ out,
+    int32_t* __restrict__ accepted_out, int64_t* __restrict__ row_tokens_out, int use_candidates) {
+    __shared__ SampleShared sh;
+    const int row_id = blockIdx.x;
+    const int elem = DT == 2 ? 4 : 2;
+    SampleRow r = {};
+    r.row = reinterpret_cast<const char*>(logits) + (int64_t)row_id * row_stride * elem;
+    r.vocab = vocab;
+    r.vec = (reinterpret_cast<uintptr_t>(r.row) & (uintptr_t)(4 * elem - 1)) == 0;
+    r.top_k = top_ks[row_id];
+    r.temperature = probs_mode ? 1.0f : temperatures[row_id];
+    r.probs_mode = probs_mode;
+    r.row_id = row_id;
+    r.token_out = out + (int64_t)(row_id / q_len) * (q_len + 1) + 1 + row_id % q_len;
+    r.n_kept_out = nullptr;
+    r.kept_mass_out = nullptr;
+    r.draft = drafts[row_id];
+    r.accepted_out = accepted_out;
+    r.row_token_out = row_tokens_out;
+    sample_row_max<DT>(sh, r);
+    if (r.top_k == 1) {
+        if (threadIdx.x == 0) sample_emit<true>(r, r.arg_max, (int64_t)r.draft == r.arg_max);
+        return;
+    }
+    r.top_p = top_ps[row_id];
+    r.u_acc = uniforms[2 * (int64_t)row_id];
+    r.u = uniforms[2 * (int64_t)row_id + 1];
+    sample_row_draw<DT, true>(sh, r, use_candidates);
+}
+
+// Sequence stage: one thread per sequence.  n_ok = the leading accepted rows among the first T - 1; the sequence emits
+// tok[0 .. n_ok] (the accepted drafts, then the replacement or bonus token): out[b] = [n_ok + 1, tok[0 .. n_ok], -1 ...].
+constexpr int kVerifyMaxQ = 8;  // the larger of the two multi-token decodes' query lengths (kGqaMultiMaxQ, kMlaMultiMaxQ)
+__global__ __launch_bounds__(256) void verify_sequences_kernel(int64_t* __restrict__ out, int bs, int q_len) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= bs) return;
+    int64_t* o = out + (int64_t)b * (q_len + 1);
+    int64_t v[kVerifyMaxQ];
+#pragma unroll
+    for (int t = 0; t < kVerifyMaxQ; ++t) v[t] = t < q_len ? o[1 + t] : 0;
+    int n_ok = 0;
+    bool leading = true;
+#pragma unroll
+    for (int t = 0; t < kVerifyMaxQ - 1; ++t) {
+        leading = leading && t < q_len - 1 && (v[t] & kVerifyAcceptedBit) != 0;
+        n_ok += leading ? 1 : 0;
+    }
+    o[0] = n_ok + 1;
+#pragma unroll
+    for (int t = 0; t < kVerifyMaxQ; ++t)
+        if (t < q_len) o[1 + t] = t <= n_ok ? (v[t] & ~kVerifyAcceptedBit) : (int64_t)-1;
 }
 
 // logits[row, token] -= penalty[row] once per occurrence of `token` in the row's generated tokens
@@ -731,5 +952,32 @@ extern "C" int chitu_hip_sample(const void* logits, int act_dtype, int64_t row_s
     else if (act_dtype == 1) LAUNCH(1);
     else LAUNCH(2);
 #undef LAUNCH
+    CHITU_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int chitu_hip_speculative_verify(const void* logits, int act_dtype, int64_t row_stride, int64_t rows, int32_t vocab,
+                                            const float* temperatures, const int32_t* top_ks, const float* top_ps,
+                                            const int32_t* drafts, const float* uniforms, int32_t q_len, int32_t probs_mode,
+                                            int64_t* out, int32_t* accepted_out, int64_t* row_tokens_out, void* stream) {
+    CHITU_REQUIRE(logits && out && rows >= 0 && vocab > 0 && row_stride >= vocab);
+    CHITU_REQUIRE(act_dtype >= 0 && act_dtype <= 2);
+    CHITU_REQUIRE(probs_mode == 0 || probs_mode == 1);
+    CHITU_REQUIRE(top_ks && top_ps && drafts && uniforms && (probs_mode || temperatures));
+    CHITU_REQUIRE(q_len >= 2 && q_len <= chitu::kVerifyMaxQ && rows % q_len == 0);
+    CHITU_REQUIRE(rows <= 0x7fffffff);
+    if (rows == 0) return CHITU_OK;
+    const int use_candidates = chitu::debug_option(chitu::kOptSampleRadix) > 0 ? 0 : 1;  // as chitu_hip_sample
+#define LAUNCH(DT)                                                                                              \
+    hipLaunchKernelGGL(chitu::verify_rows_kernel<DT>, dim3((unsigned)rows), dim3(chitu::kSampleThreads), 0,     \
+                       (hipStream_t)stream, logits, row_stride, (int)vocab, temperatures, top_ks, top_ps, drafts, \
+                       uniforms, (int)q_len, (int)probs_mode, out, accepted_out, row_tokens_out, use_candidates)
+    if (act_dtype == 0) LAUNCH(0);
+    else if (act_dtype == 1) LAUNCH(1);
+    else LAUNCH(2);
+#undef LAUNCH
+    // the kernel boundary orders the two stages (a hand-off inside one launch loses to it here: DESIGN 3.9)
+    const int bs = (int)(rows / q_len);
+    hipLaunchKernelGGL(chitu::verify_sequences_kernel, dim3((unsigned)((bs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, bs,
+                       (int)q_len);
     CHITU_RETURN_LAUNCH_STATUS();
 }

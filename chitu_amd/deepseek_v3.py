@@ -831,11 +831,25 @@ class DeepSeekV3Decoder(torch.nn.Module):
         plain greedy generate() picks, in fewer steps when the drafter is right (drafter.propose(history, draft_len); a
         DeepSeek-V3 checkpoint's multi-token-prediction head is such a drafter, chitu_amd.sampling.NgramDrafter another).
         Returns [n_req, max_new_tokens] int64 and frees the requests' pages; self.speculative_stats = {"steps", "accepted",
-        "drafted"}.  Greedy only: any sampling argument raises; draft_len outside 1 .. 7 raises."""
+        "drafted"}.  Greedy only: any sampling argument raises (generate_speculative_sampled takes them); draft_len outside 1 .. 7 raises."""
         from . import sampling
 
         return sampling.generate_speculative_greedy(self, prompts, max_new_tokens, drafter, draft_len, MLA_MULTI_MAX_Q, req_ids, use_graph,
                                                     (temperatures, top_ks, top_ps, frequency_penalties, generator))
+
+    @torch.inference_mode()
+    def generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, temperatures=None, top_ks=None, top_ps=None,
+                                     frequency_penalties=None, generator=None, req_ids=None, use_graph=True):
+        """generate_speculative with generate()'s sampling parameters, LlamaDecoder.generate_speculative_sampled's contract on
+        this decoder's decode_multi: one chitu_hip_speculative_verify call per round accepts a draft d with probability p(d)
+        under the distribution p generate()'s sampler draws from, and replaces the first rejected draft by a draw from p without
+        d, renormalised.  Drafters are deterministic proposals (a drafter that samples its proposals would need its
+        probabilities in the rule: out of scope).  The output tokens are distributed as generate()'s but come from another
+        uniform stream.  With every top_k <= 1 the result is generate_speculative's."""
+        from . import sampling
+
+        return sampling.generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, MLA_MULTI_MAX_Q, temperatures,
+                                                     top_ks, top_ps, frequency_penalties, generator, req_ids, use_graph)
 
 
 def _check_multi_step_rows(rows: int):

@@ -382,13 +382,37 @@ class LlamaDecoder(torch.nn.Module):
         accepted, the argmax at the first mismatch (or after the last draft) is emitted as the bonus token, and the cache
         keeps accepted + 1 rows.  A request leaves the batch when it has max_new_tokens.  Returns [n_req, max_new_tokens] int64
         and frees the requests' pages; self.speculative_stats = {"steps": verify steps run, "accepted": drafts accepted,
-        "drafted": drafts proposed}.  Greedy only: any sampling argument raises.  The drafter runs on the host: the accepted
+        "drafted": drafts proposed}.  Greedy only: any sampling argument raises (generate_speculative_sampled takes them).  The drafter runs on the host: the accepted
         counts have to reach the host for the page accounting anyway (one small copy per round).  Every request needs room
         for draft_len tokens beyond prompt + max_new_tokens in its block table."""
         from . import sampling
 
         return sampling.generate_speculative_greedy(self, prompts, max_new_tokens, drafter, draft_len, GQA_MULTI_MAX_Q, req_ids, use_graph,
                                                     (temperatures, top_ks, top_ps, frequency_penalties, generator))
+
+    @torch.inference_mode()
+    def generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, temperatures=None, top_ks=None, top_ps=None,
+                                     frequency_penalties=None, generator=None, req_ids=None, use_graph=True):
+        """generate_speculative's draft-and-verify loop with generate()'s sampling parameters (per request: temperature, top_k,
+        top_p, frequency penalty; `generator`: a CUDA torch.Generator for the uniforms).  The first token is sampled from the
+        prefill logits.  Each round ONE decode_multi step runs over [last token | drafts] and ONE chitu_hip_speculative_verify
+        call judges the drafts on the device: under the distribution p that generate()'s sampler draws from for the row, a
+        draft d is accepted with probability p(d); the first rejected draft is replaced by a draw from p without d,
+        renormalised; after draft_len accepted drafts a bonus token is drawn from p.  The frequency penalty of row t counts the
+        response so far and the round's drafts before t.
+
+        Drafters are deterministic proposals: drafter.propose(history, draft_len) names tokens, and the rule above is rejection
+        sampling against a point mass.  A drafter that samples its proposals would have to hand over their probabilities
+        (accept with min(1, p / q), replace from max(p - q, 0)): out of scope here.  The output tokens are distributed as
+        generate()'s with the same parameters, but they come from another uniform stream: the same generator seed does not
+        give generate()'s tokens.  With every top_k <= 1 the result is generate_speculative's.
+
+        Returns [n_req, max_new_tokens] int64, frees the requests' pages, leaves self.speculative_stats as generate_speculative
+        does.  draft_len outside 1 .. 7 raises."""
+        from . import sampling
+
+        return sampling.generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, GQA_MULTI_MAX_Q, temperatures,
+                                                     top_ks, top_ps, frequency_penalties, generator, req_ids, use_graph)
 
 
 @torch.no_grad()

@@ -14,6 +14,10 @@ documents -1 that way; the reference's mask zeroes the whole row and multinomial
 sorted order go to the lower token id (torch.sort leaves them unspecified); the draw is an inverse CDF
 driven by one uniform per row from a torch.Generator (multinomial's exponential-race draw has the same
 distribution but another stream).
+
+No reference counterpart: speculative decoding.  `generate_speculative_greedy` / `generate_speculative_sampled` are the
+draft-and-verify loops of the decoders' generate_speculative / generate_speculative_sampled; the sampled one judges the drafts on the
+device with ONE `chitu_hip_speculative_verify` call per round (`speculative_verify`; rule and proof in DESIGN 3.9).
 """
 
 from typing import List, Optional, Sequence, Tuple
@@ -31,6 +35,9 @@ __all__ = [
     "sample_tokens",
     "DeviceSampler",
     "NgramDrafter",
+    "speculative_verify",
+    "generate_speculative_greedy",
+    "generate_speculative_sampled",
 ]
 
 
@@ -233,17 +240,84 @@ class NgramDrafter:
         return out + [fill] * (k - len(out))
 
 
+def speculative_verify(logits, drafts, T, temperatures, top_ks, top_ps, uniforms=None, generator=None, probs_mode=False,
+                       return_rows=False):
+    """Draft verification of speculative decoding with sampling, one call (chitu_hip_speculative_verify: a launch over the rows and a
+    tiny one over the sequences; new: the reference has no speculative path).  logits [bs * T, vocab] (or [bs, T, vocab]): row (b, t) is the target model's distribution for the token
+    after position t of sequence b, under the row's temperature / top_k / top_p exactly as top_k_top_p_sampling_from_logits
+    draws from it (probs_mode: the rows are probabilities, temperatures may be None).  drafts [bs * T] int32: the deterministic
+    proposal for that token, -1 at each sequence's last row.  A draft d is accepted with probability p(d); the first rejected
+    row emits a draw from p without d, renormalised, and the row after the last draft a plain draw -- so every emitted token is
+    distributed as p.  uniforms [bs * T, 2] in [0, 1) (acceptance, replacement) make the result reproducible; otherwise they come
+    from `generator` (a CUDA torch.Generator) or the default one.
+
+    Returns out [bs, T + 1] int64 on the device: column 0 the number of emitted tokens (leading accepted drafts + 1), then the
+    tokens, then -1.  return_rows: also (accepted [bs * T] int32, row_tokens [bs * T] int64), the per-row results."""
+    require_cuda(logits)
+    x2, rows, vocab = _rows(logits)
+    T = int(T)
+    if T < 2 or rows % T:
+        raise ValueError(f"speculative_verify: {rows} rows are not sequences of T={T} >= 2 rows")
+    dev = logits.device
+    d = _per_row(drafts, rows, torch.int32, dev)
+    if uniforms is None:
+        u = torch.rand(rows, 2, dtype=torch.float32, device=dev, generator=generator)
+    else:
+        u = _per_row(uniforms, rows * 2, torch.float32, dev)
+    temps = None if probs_mode and temperatures is None else _per_row(temperatures, rows, torch.float32, dev)
+    ks, ps = _per_row(top_ks, rows, torch.int32, dev), _per_row(top_ps, rows, torch.float32, dev)
+    out = torch.empty(rows // T, T + 1, dtype=torch.int64, device=dev)
+    accepted = row_tokens = None
+    if return_rows:
+        accepted = torch.empty(rows, dtype=torch.int32, device=dev)
+        row_tokens = torch.empty(rows, dtype=torch.int64, device=dev)
+    check(_lib.lib().chitu_hip_speculative_verify(ptr(x2), float_dtype_code(x2.dtype), i64(x2.stride(0)), i64(rows), i32(vocab),
+                                                  ptr(temps), ptr(ks), ptr(ps), ptr(d), ptr(u), i32(T), i32(1 if probs_mode else 0),
+                                                  ptr(out), ptr(accepted), ptr(row_tokens), stream_ptr()), "speculative_verify")
+    return (out, accepted, row_tokens) if return_rows else out
+
+
+def _check_draft_len(draft_len, max_q):
+    if not 1 <= draft_len <= max_q - 1:
+        raise ValueError(f"draft_len={draft_len}: a verify step holds the last token and 1 .. {max_q - 1} drafts")
+
+
+def _propose_drafts(drafter, prompts, out, live, draft_len):
+    """draft_len tokens per live request from the drafter, history = prompt + tokens so far"""
+    drafts = []
+    for i in live:
+        d = [int(t) for t in drafter.propose(list(prompts[i]) + out[i], draft_len)]
+        assert len(d) == draft_len, f"drafter proposed {len(d)} tokens, not draft_len={draft_len}"
+        drafts.append(d)
+    return drafts
+
+
+def _retire_finished(model, req_ids, out, live, max_new_tokens):
+    """requests that have max_new_tokens leave the batch and return their pages"""
+    for i in [i for i in live if len(out[i]) >= max_new_tokens]:
+        model.cache.finalize_cache_all_decode(req_ids[i])
+        live.remove(i)
+
+
+def _finish_speculative(model, out, stats, max_new_tokens):
+    from . import tensor_parallel as tp
+
+    model.speculative_stats = stats
+    if tp.xgmi_comm() is not None:
+        torch.cuda.current_stream().synchronize()
+        tp.check_comm()
+    return torch.tensor([o[:max_new_tokens] for o in out], dtype=torch.int64, device=model.device)
+
+
 def generate_speculative_greedy(model, prompts, max_new_tokens, drafter, draft_len, max_q, req_ids=None, use_graph=True,
                                 sampling_args=()):
     """The draft-and-verify loop of LlamaDecoder / DeepSeekV3Decoder.generate_speculative (their docstrings state the contract):
     model-independent, it needs model.prefill, model.decode_multi, model.cache and model.device, and leaves
     model.speculative_stats.  max_q: the most tokens a verify step of the model holds (the last token + max_q - 1 drafts)."""
-    from . import tensor_parallel as tp
-
     if any(a is not None for a in sampling_args):
-        raise NotImplementedError("generate_speculative is greedy: the acceptance rule draft == argmax has no sampling form here")
-    if not 1 <= draft_len <= max_q - 1:
-        raise ValueError(f"draft_len={draft_len}: a verify step holds the last token and 1 .. {max_q - 1} drafts")
+        raise NotImplementedError("generate_speculative is greedy (it accepts a draft iff draft == argmax): "
+                                  "generate_speculative_sampled takes temperatures, top_ks, top_ps and frequency_penalties")
+    _check_draft_len(draft_len, max_q)
     n_req = len(prompts)
     req_ids = [f"gen{i}" for i in range(n_req)] if req_ids is None else list(req_ids)
     T = draft_len + 1
@@ -256,11 +330,7 @@ def generate_speculative_greedy(model, prompts, max_new_tokens, drafter, draft_l
         for r in req_ids:
             model.cache.finalize_cache_all_decode(r)
     while live:
-        drafts = []
-        for i in live:
-            d = [int(t) for t in drafter.propose(list(prompts[i]) + out[i], draft_len)]
-            assert len(d) == draft_len, f"drafter proposed {len(d)} tokens, not draft_len={draft_len}"
-            drafts.append(d)
+        drafts = _propose_drafts(drafter, prompts, out, live, draft_len)
         ids = [req_ids[i] for i in live]
         model.cache.prepare_block_table_for_decode_multi(ids, T)
         step = torch.tensor([[out[i][-1]] + d for i, d in zip(live, drafts)], dtype=torch.int64, device=model.device)
@@ -277,11 +347,62 @@ def generate_speculative_greedy(model, prompts, max_new_tokens, drafter, draft_l
             stats["drafted"] += draft_len
         stats["steps"] += 1
         model.cache.finalize_cache_multi_decode(ids, kept)
-        for i in [i for i in live if len(out[i]) >= max_new_tokens]:
-            model.cache.finalize_cache_all_decode(req_ids[i])
-            live.remove(i)
-    model.speculative_stats = stats
-    if tp.xgmi_comm() is not None:
-        torch.cuda.current_stream().synchronize()
-        tp.check_comm()
-    return torch.tensor([o[:max_new_tokens] for o in out], dtype=torch.int64, device=model.device)
+        _retire_finished(model, req_ids, out, live, max_new_tokens)
+    return _finish_speculative(model, out, stats, max_new_tokens)
+
+
+def generate_speculative_sampled(model, prompts, max_new_tokens, drafter, draft_len, max_q, temperatures, top_ks, top_ps,
+                                 frequency_penalties=None, generator=None, req_ids=None, use_graph=True):
+    """generate_speculative_greedy's loop with the acceptance rule in sampling form (the decoders' generate_speculative_sampled
+    docstrings state the contract).  The first token is sampled from the prefill logits as DeviceSampler does.  Each round: with
+    any penalty > 0, row (b, t) of the verify logits is penalised with response[b] + drafts[b][:t] (what the response would be if
+    the drafts before t are accepted -- and row t only counts if they are) in one launch over the bs * T rows; then ONE
+    speculative_verify call and ONE copy of its [bs, T + 1] result to the host.  If every top_k <= 1 the rows are greedy rows
+    of the same kernel (accepted iff draft == argmax): generate_speculative_greedy's tokens."""
+    _check_draft_len(draft_len, max_q)
+    n_req = len(prompts)
+    req_ids = [f"gen{i}" for i in range(n_req)] if req_ids is None else list(req_ids)
+    T = draft_len + 1
+    ks = [1] * n_req if top_ks is None else [int(k) for k in (top_ks.tolist() if isinstance(top_ks, torch.Tensor) else top_ks)]
+    if all(k <= 1 for k in ks):  # `is_all_greedy` (task.py:457), as in sample_tokens / DeviceSampler
+        ks = [1] * n_req
+
+    def as_list(v, default):
+        return [default] * n_req if v is None else [float(x) for x in (v.tolist() if isinstance(v, torch.Tensor) else v)]
+
+    temps, ps, pens = as_list(temperatures, 1.0), as_list(top_ps, 1.0), as_list(frequency_penalties, 0.0)
+    assert len(ks) == len(temps) == len(ps) == len(pens) == n_req
+    penalise = any(p > 0 for p in pens)
+    first = sample_tokens(model.prefill(prompts, req_ids), temps, ks, ps, generator=generator).tolist()
+    out = [[t] for t in first]
+    stats = {"steps": 0, "accepted": 0, "drafted": 0}
+    live = list(range(n_req))
+    if max_new_tokens <= 1:
+        live = []
+        for r in req_ids:
+            model.cache.finalize_cache_all_decode(r)
+    params_of = None  # the per-row parameters on the device, rebuilt when a request leaves the batch
+    while live:
+        drafts = _propose_drafts(drafter, prompts, out, live, draft_len)
+        ids = [req_ids[i] for i in live]
+        model.cache.prepare_block_table_for_decode_multi(ids, T)
+        step = torch.tensor([[out[i][-1]] + d for i, d in zip(live, drafts)], dtype=torch.int64, device=model.device)
+        logits = model.decode_multi(step, use_graph=use_graph).view(len(live) * T, -1)
+        if penalise:
+            apply_frequency_penalty(logits, [out[i] + d[:t] for i, d in zip(live, drafts) for t in range(T)],
+                                    [pens[i] for i in live for _ in range(T)])
+        if params_of != live:
+            params_of = list(live)
+            dev_params = [_per_row([v[i] for i in live for _ in range(T)], len(live) * T, dt, model.device)
+                          for v, dt in ((temps, torch.float32), (ks, torch.int32), (ps, torch.float32))]
+        res = speculative_verify(logits, [t for d in drafts for t in d + [-1]], T, *dev_params, generator=generator).tolist()
+        kept = []
+        for i, row in zip(live, res):
+            out[i].extend(row[1 : 1 + row[0]])
+            kept.append(row[0])
+            stats["accepted"] += row[0] - 1
+            stats["drafted"] += draft_len
+        stats["steps"] += 1
+        model.cache.finalize_cache_multi_decode(ids, kept)
+        _retire_finished(model, req_ids, out, live, max_new_tokens)
+    return _finish_speculative(model, out, stats, max_new_tokens)

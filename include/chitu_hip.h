@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 10  /* 10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 11  /* 11: + chitu_hip_speculative_verify (draft verification of speculative decoding with sampling, next to chitu_hip_sample), additive only.  10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -940,6 +940,23 @@ int chitu_hip_sample(const void* logits, int act_dtype, int64_t row_stride, int6
                      const float* temperatures, const int32_t* top_ks, const float* top_ps,
                      const float* uniforms, int32_t probs_mode, int64_t* out_tokens,
                      int32_t* n_kept_out, float* kept_mass_out, void* stream);
+/*   chitu_hip_speculative_verify  new: no reference counterpart.  Draft verification of speculative decoding with sampling:
+ *     the draft d of a row is accepted with probability p(d), p being the distribution chitu_hip_sample draws from for that row;
+ *     a rejected row emits a draw from p with d removed and the rest renormalised, so every emitted token is distributed as p.
+ *     logits [rows, vocab], act_dtype, row_stride, temperatures / top_ks / top_ps [rows] and probs_mode as chitu_hip_sample
+ *     (all arrays required; temperatures may be NULL in probs_mode); rows = bs * q_len, 2 <= q_len <= 8, row b * q_len + t
+ *     judges the token after position t of sequence b.  drafts [rows] i32: the proposed token, < 0 for none (each sequence's
+ *     last row).  uniforms [rows, 2] f32 in [0, 1): (u_acc, u_alt).  In the sampler's integers (K the kept set, w_i = floor(e_i *
+ *     2^40), S = sum_K w_i, target(u, s) = min(floor(u * s), s - 1)): top_k == 1 or S == 0 -> accepted iff d == arg-max, token
+ *     = arg-max; else w_d = d's kept weight (0 if d is not kept or >= vocab), accepted iff target(u_acc, S) < w_d with token = d,
+ *     otherwise token = inverse CDF in index order over K \ {d} at target(u_alt, S - w_d); d < 0 -> not accepted, token =
+ *     chitu_hip_sample's for u_alt.  out [bs, q_len + 1] i64: n_ok = leading accepted rows among the first q_len - 1 of the
+ *     sequence; out[b] = [n_ok + 1, token of rows 0 .. n_ok, -1 ...].  accepted_out [rows] i32 / row_tokens_out [rows] i64
+ *     (the per-row results) are optional.  Two launches on `stream`; rows == 0 launches nothing. */
+int chitu_hip_speculative_verify(const void* logits, int act_dtype, int64_t row_stride, int64_t rows, int32_t vocab,
+                                 const float* temperatures, const int32_t* top_ks, const float* top_ps,
+                                 const int32_t* drafts, const float* uniforms, int32_t q_len, int32_t probs_mode,
+                                 int64_t* out, int32_t* accepted_out, int64_t* row_tokens_out, void* stream);
 
 /* ---- in-graph tensor-parallel collectives over xGMI (csrc/comm.hip) --------------------------------
  * Replace the NCCL calls of the reference's decode step -- dist.all_reduce after every RowParallelLinear
