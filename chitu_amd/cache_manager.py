@@ -342,6 +342,24 @@ class PagedKVCacheManager:
         self.curr_varlens = None
         self.curr_req_ids = None
 
+    def rollback(self, req_ids, n_drop):
+        """Give rows back: request b's length shrinks by n_drop[b] >= 0 and the pages beyond ceil(length / block_size) return to
+        the free list (finalize_cache_multi_decode's invariant; `_table_rows` goes stale when a page left).  The rows are only
+        forgotten -- they stay behind the length as garbage, and no kernel uses bytes past a length -- so dropping more rows than
+        were decoded since prefill is allowed; dropping below 0 raises before anything changes.  A draft model's cache uses this
+        to return to what the target accepted (sampling.ModelDrafter.settle)."""
+        assert len(req_ids) == len(n_drop)
+        drops = [int(d) for d in n_drop]
+        for req_id, d in zip(req_ids, drops):
+            if d < 0 or d > self.seq_lens[req_id]:
+                raise ValueError(f"request {req_id!r}: cannot drop {d} of {self.seq_lens[req_id]} cached rows")
+        for req_id, d in zip(req_ids, drops):
+            self.seq_lens[req_id] -= d
+            keep = (self.seq_lens[req_id] + self.block_size - 1) // self.block_size
+            while len(self.block_table[req_id]) > keep:
+                self.free_blocks.append(self.block_table[req_id].pop())
+                self._table_rows = None
+
     def finalize_cache_single_decode(self, req_ids):
         for req_id in req_ids:
             self.seq_lens[req_id] = self.seq_lens[req_id] + 1

@@ -23,6 +23,8 @@
 //
 // chitu_hip_speculative_verify (below, new: no reference counterpart) is the same row with a draft token: the passes are
 // shared, and the acceptance test sits between the kept prefix and the draw.
+#include <type_traits>
+
 #include "common.h"
 
 namespace chitu {
@@ -72,13 +74,17 @@ __device__ __forceinline__ float ordered_key_inv(uint32_t k) {
 }
 
 // Four consecutive elements i0 .. i0+3 of a row (i0 % 4 == 0, i0 < vocab); returns how many are in
-// range.  `vec`: the row start is 16-B (f32) / 8-B (16-bit types) aligned, so one wide load is legal.
+// range.  `vec` bit 0: the row start is 16-B (f32) / 8-B (16-bit types) aligned, so one wide load is legal.  DT 3: the element
+// type is a run-time value (act_dtype) in vec's bits above bit 0 -- the verification against a sampled draft reads two rows of
+// independent types and is compiled once.
 template <int DT>
-__device__ __forceinline__ int load4(const void* row, int i0, int vocab, bool vec, float (&v)[4]) {
+__device__ __forceinline__ int load4(const void* row, int i0, int vocab, int vec, float (&v)[4]) {
     const int n = min(4, vocab - i0);
-    if (DT == 2) {
+    const int dt = DT == 3 ? (vec >> 1) : DT;
+    const bool wide = (vec & 1) && n == 4;
+    if (dt == 2) {
         const float* p = reinterpret_cast<const float*>(row) + i0;
-        if (vec && n == 4) {
+        if (wide) {
             const f32x4 t = *reinterpret_cast<const f32x4*>(p);
 #pragma unroll
             for (int k = 0; k < 4; ++k) v[k] = t[k];
@@ -89,7 +95,7 @@ __device__ __forceinline__ int load4(const void* row, int i0, int vocab, bool ve
     } else {
         const uint16_t* p = reinterpret_cast<const uint16_t*>(row) + i0;
         uint16_t h[4];
-        if (vec && n == 4) {
+        if (wide) {
             const i32x2 t = *reinterpret_cast<const i32x2*>(p);
             h[0] = (uint16_t)((uint32_t)t[0] & 0xffffu);
             h[1] = (uint16_t)((uint32_t)t[0] >> 16);
@@ -100,7 +106,7 @@ __device__ __forceinline__ int load4(const void* row, int i0, int vocab, bool ve
             for (int k = 0; k < 4; ++k) h[k] = k < n ? p[k] : (uint16_t)0;
         }
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = DT == 0 ? bf16_to_f32(h[k]) : f16_to_f32(h[k]);
+        for (int k = 0; k < 4; ++k) v[k] = dt == 0 ? bf16_to_f32(h[k]) : f16_to_f32(h[k]);
     }
     return n;
 }
@@ -112,15 +118,24 @@ __device__ __forceinline__ int load4(const void* row, int i0, int vocab, bool ve
 // every chunk (n = 0 for lanes past the end of the row), so it may use wave-wide operations.
 constexpr int kSampleUnroll = 8;
 template <int DT, int U, typename F>
-__device__ __forceinline__ void for_each_quad(const void* row, int vocab, bool vec, F&& body) {
+__device__ __forceinline__ void for_each_quad(const void* row, int vocab, int vec, F&& body) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int base = wave * 256; base < vocab; base += kSampleThreads * 4 * U) {  // wave-uniform trip count
         float v[U][4];
         int n[U];
+        auto load_all = [&](auto dt) {
 #pragma unroll
-        for (int q = 0; q < U; ++q) {
-            const int i0 = base + q * kSampleThreads * 4 + lane * 4;
-            n[q] = i0 < vocab ? load4<DT>(row, i0, vocab, vec, v[q]) : 0;
+            for (int q = 0; q < U; ++q) {
+                const int i0 = base + q * kSampleThreads * 4 + lane * 4;
+                n[q] = i0 < vocab ? load4<decltype(dt)::value>(row, i0, vocab, vec & 1, v[q]) : 0;
+            }
+        };
+        if constexpr (DT == 3) {  // one branch around the U loads, so they stay in flight together
+            if ((vec >> 1) == 2) load_all(std::integral_constant<int, 2>{});
+            else if ((vec >> 1) == 0) load_all(std::integral_constant<int, 0>{});
+            else load_all(std::integral_constant<int, 1>{});
+        } else {
+            load_all(std::integral_constant<int, DT>{});
         }
 #pragma unroll
         for (int q = 0; q < U; ++q) {
@@ -166,7 +181,7 @@ struct SampleShared {
 // wave's first active lane are combined in registers first (two rounds): flat distributions put
 // most of the vocabulary in a handful of bins and same-address LDS atomics serialise.
 template <int DT>
-__device__ __forceinline__ void sample_hist_level(SampleShared& sh, const void* row, int vocab, bool vec,
+__device__ __forceinline__ void sample_hist_level(SampleShared& sh, const void* row, int vocab, int vec,
                                                   float temperature, float m, int probs_mode, int shift,
                                                   bool use_prefix, uint32_t prefix) {
     const int tid = threadIdx.x, lane = tid & 63;
@@ -355,7 +370,7 @@ __device__ __forceinline__ uint64_t sample_target(float u, uint64_t s) {
 struct SampleRow {
     const void* row;
     int vocab;
-    bool vec;
+    int vec;  // load4's
     float temperature;
     int probs_mode;
     int top_k;
@@ -428,7 +443,7 @@ template <int DT, bool VERIFY>
 __device__ __forceinline__ bool sample_candidates(SampleShared& sh, const SampleRow& r) {
     const void* row = r.row;
     const int vocab = r.vocab, probs_mode = r.probs_mode, top_k = r.top_k;
-    const bool vec = r.vec;
+    const int vec = r.vec;
     const float temperature = r.temperature, m = r.m, top_p = r.top_p;
     const int tid = threadIdx.x, lane = tid & 63;
     uint64_t* arr = sh.sum;  // the histogram's sum array doubles as the sort buffer (kCandCap == kSampleBins)
@@ -556,7 +571,7 @@ template <int DT>
 __device__ __forceinline__ SampleCut sample_radix_cut(SampleShared& sh, const SampleRow& r) {
     const void* row = r.row;
     const int vocab = r.vocab, probs_mode = r.probs_mode, top_k = r.top_k;
-    const bool vec = r.vec;
+    const int vec = r.vec;
     const float temperature = r.temperature, m = r.m, top_p = r.top_p;
     uint32_t k_rem = top_k <= 0 ? 0xffffffffu : (uint32_t)top_k;  // <= 0: no top-k limit
     uint64_t p_rem = 0;
@@ -901,6 +916,308 @@ __global__ __launch_bounds__(256) void verify_sequences_kernel(int64_t* __restri
         if (t < q_len) o[1 + t] = t <= n_ok ? (v[t] & ~kVerifyAcceptedBit) : (int64_t)-1;
 }
 
+// ---------------------------------------------------------------- speculative decoding: verification against a sampled draft
+// Row stage of chitu_hip_speculative_verify_sampled (new: no reference counterpart): the draft d of row (b, t) was DRAWN from the
+// draft model's distribution q for that position, so the row comes with q's logits, and q is cut under the row's own temperature /
+// top_k / top_p exactly as p is (the drafter samples under the request's parameters).  With w_i, S_p the kept integer weights of
+// the target row and v_i, S_q those of the draft row, and U(u) = min(floor(u * 2^24), 2^24 - 1):
+//     accepted iff U(u_acc) * v_d * S_p < 2^24 * w_d * S_q                  (probability min(1, p(d) / q(d)) on the 2^-24 grid)
+//     else token = inverse CDF in index order over r_i = max(0, w_i * S_q - v_i * S_p) at floor(U(u_alt) * R / 2^24), R = sum r_i
+// -- the residual max(p - q, 0), renormalised, in integers (p_i - q_i = r_i / (S_p * S_q)).  The products reach 2^125, so the
+// arithmetic is unsigned __int128 (multiplies, adds, subtracts, compares and shifts only: no 128-bit division).  Greedy rows, rows
+// with S_p == 0 or S_q == 0 and rows without a draft are verify_rows_kernel's.  The specification is tests/spec_verify_sampled_ref.py.
+//
+// Passes over the pair after the two radix cuts (each wave owns one contiguous segment of the vocabulary, as in the draw):
+//   count     ties at either cut per segment, and the draft's entry in both rows -> the acceptance test;
+//   residual  (rejected rows only) r_i of the segment summed in 128 bits; a tie's rank among its row's ties in index order decides
+//             whether it is kept, hence the count pass first;
+//   rescan    the one wave whose segment holds the position walks it with prefix sums and emits the token.
+// Every pass loads a lane's four elements of BOTH rows before it uses either.
+typedef unsigned __int128 u128;
+constexpr int kRuntimeDT = 3;  // load4: both rows' element types are run-time values, so the pair kernel is compiled once
+
+struct VerifyPairShared {
+    SampleShared s;
+    uint32_t ties_p[kSampleWaves], ties_q[kSampleWaves];    // ties at the row's tau inside the segment
+    uint32_t below_p[kSampleWaves], below_q[kSampleWaves];  // of those, the ones below the draft's index
+    uint64_t draft_p[kSampleWaves], draft_q[kSampleWaves];  // the draft's entry: its weight above tau, or kDraftIsTie
+    uint64_t res_lo[kSampleWaves], res_hi[kSampleWaves];    // the segment's residual sum
+};
+
+__device__ __forceinline__ u128 make_u128(uint64_t hi, uint64_t lo) { return ((u128)hi << 64) | (u128)lo; }
+__device__ __forceinline__ u128 shfl_up_u128(u128 v, int off) {
+    return make_u128(shfl_up_u64((uint64_t)(v >> 64), off), shfl_up_u64((uint64_t)v, off));
+}
+__device__ __forceinline__ u128 shfl_xor_u128(u128 v, int off) {
+    return make_u128(shfl_xor_u64((uint64_t)(v >> 64), off), shfl_xor_u64((uint64_t)v, off));
+}
+__device__ __forceinline__ uint64_t shfl_lane_u64(uint64_t v, int l) {
+    return ((uint64_t)(uint32_t)__shfl((int)(v >> 32), l, 64) << 32) | (uint32_t)__shfl((int)(uint32_t)v, l, 64);
+}
+
+// U(u): the uniform on the 2^-24 grid (u * 2^24 is exact in f32; NaN -> 0)
+__device__ __forceinline__ uint64_t verify_grid(float u) {
+    const float c = __builtin_fminf(__builtin_fmaxf(u, 0.f), 1.f);
+    const uint32_t g = (uint32_t)(c * 16777216.0f);
+    return g < 16777215u ? g : 16777215u;
+}
+
+// The kept weights of a lane's four elements of both rows (0 where the element is not kept or past the row's end), with the
+// ranks of the ties: ties_p / ties_q are the ties before this chunk and are advanced past it.  Whole wave.
+__device__ __forceinline__ void pair_kept_quad(const SampleRow& rp, const SampleRow& rq, const SampleCut& cp, const SampleCut& cq,
+                                               int i0, int seg_end, uint32_t& ties_p, uint32_t& ties_q, uint64_t (&wp)[4],
+                                               uint64_t (&wq)[4]) {
+    const int lane = threadIdx.x & 63;
+    float vp[4] = {0.f, 0.f, 0.f, 0.f}, vq[4] = {0.f, 0.f, 0.f, 0.f};
+    int n = 0;
+    if (i0 < seg_end) {
+        n = load4<kRuntimeDT>(rp.row, i0, rp.vocab, rp.vec, vp);
+        load4<kRuntimeDT>(rq.row, i0, rq.vocab, rq.vec, vq);
+    }
+    bool tp[4], tq[4];
+    uint64_t t_l = 0;  // this lane's ties: p's in the low word, q's in the high word
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const float ep = sample_e(sample_x(vp[k], rp.temperature, rp.probs_mode), rp.m, rp.probs_mode);
+        const float eq = sample_e(sample_x(vq[k], rq.temperature, rq.probs_mode), rq.m, rq.probs_mode);
+        const uint32_t kp = __float_as_uint(ep), kq = __float_as_uint(eq);
+        tp[k] = k < n && kp == cp.tau;
+        tq[k] = k < n && kq == cq.tau;
+        wp[k] = (k < n && kp > cp.tau) ? sample_fix(ep) : 0ull;
+        wq[k] = (k < n && kq > cq.tau) ? sample_fix(eq) : 0ull;
+        t_l += (tp[k] ? 1ull : 0ull) + (tq[k] ? (1ull << 32) : 0ull);
+    }
+    uint64_t t_incl = t_l;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t o = shfl_up_u64(t_incl, off);
+        if (lane >= off) t_incl += o;
+    }
+    const uint64_t t_excl = t_incl - t_l;
+    uint32_t rank_p = ties_p + (uint32_t)t_excl, rank_q = ties_q + (uint32_t)(t_excl >> 32);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (tp[k]) {
+            if (rank_p < cp.c_keep) wp[k] = cp.e_tau;
+            ++rank_p;
+        }
+        if (tq[k]) {
+            if (rank_q < cq.c_keep) wq[k] = cq.e_tau;
+            ++rank_q;
+        }
+    }
+    const uint64_t t_all = shfl_lane_u64(t_incl, 63);
+    ties_p += (uint32_t)t_all;
+    ties_q += (uint32_t)(t_all >> 32);
+}
+
+__device__ __forceinline__ u128 pair_residual(uint64_t w, uint64_t v, uint64_t s_p, uint64_t s_q) {
+    const u128 a = (u128)w * s_q, b = (u128)v * s_p;
+    return a > b ? a - b : (u128)0;
+}
+
+__global__ __launch_bounds__(kSampleThreads) void verify_sampled_rows_kernel(
+    const void* __restrict__ logits, int64_t row_stride, const void* __restrict__ draft_logits, int64_t draft_row_stride, int vocab,
+    const float* __restrict__ temperatures, const int32_t* __restrict__ top_ks, const float* __restrict__ top_ps,
+    const int32_t* __restrict__ drafts, const float* __restrict__ uniforms, int q_len, int probs_mode, int64_t* __restrict__ out,
+    int32_t* __restrict__ accepted_out, int64_t* __restrict__ row_tokens_out, int use_candidates, int dt_p, int dt_q) {
+    __shared__ VerifyPairShared vs;
+    SampleShared& sh = vs.s;
+    const int row_id = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int elem_p = dt_p == 2 ? 4 : 2, elem_q = dt_q == 2 ? 4 : 2;
+    SampleRow r = {};
+    r.row = reinterpret_cast<const char*>(logits) + (int64_t)row_id * row_stride * elem_p;
+    r.vocab = vocab;
+    r.vec = ((reinterpret_cast<uintptr_t>(r.row) & (uintptr_t)(4 * elem_p - 1)) == 0 ? 1 : 0) | (dt_p << 1);
+    r.top_k = top_ks[row_id];
+    r.temperature = probs_mode ? 1.0f : temperatures[row_id];
+    r.probs_mode = probs_mode;
+    r.row_id = row_id;
+    r.token_out = out + (int64_t)(row_id / q_len) * (q_len + 1) + 1 + row_id % q_len;
+    r.n_kept_out = nullptr;
+    r.kept_mass_out = nullptr;
+    r.draft = drafts[row_id];
+    r.accepted_out = accepted_out;
+    r.row_token_out = row_tokens_out;
+    sample_row_max<kRuntimeDT>(sh, r);
+    if (r.top_k == 1) {
+        if (tid == 0) sample_emit<true>(r, r.arg_max, (int64_t)r.draft == r.arg_max);
+        return;
+    }
+    r.top_p = top_ps[row_id];
+    r.u_acc = uniforms[2 * (int64_t)row_id];
+    r.u = uniforms[2 * (int64_t)row_id + 1];
+    if (r.draft < 0) {  // the bonus row: chitu_hip_sample's row for u_alt; its draft row is never read
+        sample_row_draw<kRuntimeDT, true>(sh, r, use_candidates);
+        return;
+    }
+    SampleRow rq = r;
+    rq.row = reinterpret_cast<const char*>(draft_logits) + (int64_t)row_id * draft_row_stride * elem_q;
+    rq.vec = ((reinterpret_cast<uintptr_t>(rq.row) & (uintptr_t)(4 * elem_q - 1)) == 0 ? 1 : 0) | (dt_q << 1);
+    sample_row_max<kRuntimeDT>(sh, rq);
+    const SampleCut cp = sample_radix_cut<kRuntimeDT>(sh, r);
+    __syncthreads();  // every thread has read the target row's last level
+    const SampleCut cq = sample_radix_cut<kRuntimeDT>(sh, rq);
+    const uint64_t s_p = cp.s_kept, s_q = cq.s_kept;
+    if (s_p == 0 || s_q == 0) {  // a row without positive weight: the greedy rule
+        if (tid == 0) sample_emit<true>(r, r.arg_max, (int64_t)r.draft == r.arg_max);
+        return;
+    }
+    const int seg_len = ((vocab + kSampleWaves - 1) / kSampleWaves + 255) / 256 * 256;
+    const int seg_begin = min(wave * seg_len, vocab), seg_end = min(seg_begin + seg_len, vocab);
+
+    // ---- count pass
+    {
+        uint64_t ties = 0, below = 0, dp = 0, dq = 0;  // p's counts in the low words, q's in the high words
+        for (int base = seg_begin; base < seg_end; base += 256) {
+            const int i0 = base + lane * 4;
+            if (i0 < seg_end) {
+                float vp[4], vq[4];
+                const int n = load4<kRuntimeDT>(r.row, i0, vocab, r.vec, vp);
+                load4<kRuntimeDT>(rq.row, i0, vocab, rq.vec, vq);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float ep = sample_e(sample_x(vp[k], r.temperature, probs_mode), r.m, probs_mode);
+                    const float eq = sample_e(sample_x(vq[k], rq.temperature, probs_mode), rq.m, probs_mode);
+                    const uint32_t kp = __float_as_uint(ep), kq = __float_as_uint(eq);
+                    if (k < n) {
+                        const uint64_t t = (kp == cp.tau ? 1ull : 0ull) + (kq == cq.tau ? (1ull << 32) : 0ull);
+                        ties += t;
+                        if (i0 + k < r.draft) below += t;
+                        if (i0 + k == r.draft) {
+                            dp = kp > cp.tau ? sample_fix(ep) : (kp == cp.tau ? kDraftIsTie : 0ull);
+                            dq = kq > cq.tau ? sample_fix(eq) : (kq == cq.tau ? kDraftIsTie : 0ull);
+                        }
+                    }
+                }
+            }
+        }
+        ties = wave_sum_u64(ties);
+        below = wave_sum_u64(below);
+        dp = wave_sum_u64(dp);  // one lane of one wave at the most holds the draft
+        dq = wave_sum_u64(dq);
+        if (lane == 0) {
+            vs.ties_p[wave] = (uint32_t)ties;
+            vs.ties_q[wave] = (uint32_t)(ties >> 32);
+            vs.below_p[wave] = (uint32_t)below;
+            vs.below_q[wave] = (uint32_t)(below >> 32);
+            vs.draft_p[wave] = dp;
+            vs.draft_q[wave] = dq;
+        }
+    }
+    __syncthreads();
+    uint32_t ties_p = 0, ties_q = 0;  // ties before this wave's segment
+    {
+        uint64_t ent_p = 0, ent_q = 0;
+        uint32_t rank_p = 0, rank_q = 0;
+#pragma unroll
+        for (int w = 0; w < kSampleWaves; ++w) {
+            ent_p += vs.draft_p[w];
+            ent_q += vs.draft_q[w];
+            rank_p += vs.below_p[w];
+            rank_q += vs.below_q[w];
+            if (w < wave) {
+                ties_p += vs.ties_p[w];
+                ties_q += vs.ties_q[w];
+            }
+        }
+        // a tie at tau is kept iff its rank among the row's ties in index order is below c_keep
+        const uint64_t w_d = (ent_p & kDraftIsTie) ? (rank_p < cp.c_keep ? cp.e_tau : 0ull) : ent_p;
+        const uint64_t v_d = (ent_q & kDraftIsTie) ? (rank_q < cq.c_keep ? cq.e_tau : 0ull) : ent_q;
+        // U < 2^24, v_d <= 2^40, S < 2^61 (vocab <= 2^21): both sides are below 2^125
+        const u128 lhs = (u128)(verify_grid(r.u_acc) * v_d) * s_p;
+        const u128 rhs = ((u128)w_d * s_q) << 24;
+        if (lhs < rhs) {
+            if (tid == 0) sample_emit<true>(r, (int64_t)r.draft, true);
+            return;
+        }
+    }
+
+    // ---- residual pass
+    {
+        u128 res = 0;
+        uint32_t tp = ties_p, tq = ties_q;
+        for (int base = seg_begin; base < seg_end; base += 256) {
+            uint64_t wp[4], wq[4];
+            pair_kept_quad(r, rq, cp, cq, base + lane * 4, seg_end, tp, tq, wp, wq);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) res += pair_residual(wp[k], wq[k], s_p, s_q);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) res += shfl_xor_u128(res, off);
+        if (lane == 0) {
+            vs.res_lo[wave] = (uint64_t)res;
+            vs.res_hi[wave] = (uint64_t)(res >> 64);
+        }
+    }
+    __syncthreads();
+    u128 total = 0;
+#pragma unroll
+    for (int w = 0; w < kSampleWaves; ++w) total += make_u128(vs.res_hi[w], vs.res_lo[w]);
+    // floor(U * R / 2^24) without a 128-bit division or a product above 2^128
+    const uint64_t g = verify_grid(r.u);
+    const u128 target = (total >> 24) * g + (((total & (u128)0xffffffu) * g) >> 24);
+    int wsel = -1;
+    u128 run = 0;
+    {
+        u128 cum = 0;
+#pragma unroll
+        for (int w = 0; w < kSampleWaves; ++w) {
+            const u128 s = make_u128(vs.res_hi[w], vs.res_lo[w]);
+            if (wsel < 0 && target < cum + s) {
+                wsel = w;
+                run = cum;
+            }
+            cum += s;
+        }
+    }
+    if (wsel < 0) {  // R == 0: the caller's draft was not drawn from the draft row; keep the launch defined
+        if (tid == 0) sample_emit<true>(r, r.arg_max, false);
+        return;
+    }
+    if (wave != wsel) return;
+
+    // ---- rescan by the wave whose segment holds the position
+    for (int base = seg_begin; base < seg_end; base += 256) {
+        const int i0 = base + lane * 4;
+        uint64_t wp[4], wq[4];
+        pair_kept_quad(r, rq, cp, cq, i0, seg_end, ties_p, ties_q, wp, wq);
+        u128 r4[4], s_l = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            r4[k] = pair_residual(wp[k], wq[k], s_p, s_q);
+            s_l += r4[k];
+        }
+        u128 s_incl = s_l;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u128 o = shfl_up_u128(s_incl, off);
+            if (lane >= off) s_incl += o;
+        }
+        const uint64_t hit = __builtin_amdgcn_ballot_w64(run + s_incl > target);
+        if (hit) {
+            if (lane == __builtin_ctzll(hit)) {
+                u128 acc = run + s_incl - s_l;
+                int pick = 0;
+                bool done = false;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    acc += r4[k];
+                    if (!done && acc > target) {
+                        pick = k;
+                        done = true;
+                    }
+                }
+                sample_emit<true>(r, (int64_t)(i0 + pick), false);
+            }
+            return;
+        }
+        run += make_u128(shfl_lane_u64((uint64_t)(s_incl >> 64), 63), shfl_lane_u64((uint64_t)s_incl, 63));
+    }
+    if (lane == 0) sample_emit<true>(r, r.arg_max, false);  // unreachable: the segment sums add up to R
+}
+
 // logits[row, token] -= penalty[row] once per occurrence of `token` in the row's generated tokens
 // (executor.py:89-102: index_add_ with duplicates = frequency penalty), rows with penalty <= 0
 // untouched (the reference's `> 0` test).  All addends of one address are equal, so the atomic
@@ -976,6 +1293,31 @@ extern "C" int chitu_hip_speculative_verify(const void* logits, int act_dtype, i
     else LAUNCH(2);
 #undef LAUNCH
     // the kernel boundary orders the two stages (a hand-off inside one launch loses to it here: DESIGN 3.9)
+    const int bs = (int)(rows / q_len);
+    hipLaunchKernelGGL(chitu::verify_sequences_kernel, dim3((unsigned)((bs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, bs,
+                       (int)q_len);
+    CHITU_RETURN_LAUNCH_STATUS();
+}
+
+extern "C" int chitu_hip_speculative_verify_sampled(const void* logits, int act_dtype, int64_t row_stride, const void* draft_logits,
+                                                    int draft_act_dtype, int64_t draft_row_stride, int64_t rows, int32_t vocab,
+                                                    const float* temperatures, const int32_t* top_ks, const float* top_ps,
+                                                    const int32_t* drafts, const float* uniforms, int32_t q_len, int32_t probs_mode,
+                                                    int64_t* out, int32_t* accepted_out, int64_t* row_tokens_out, void* stream) {
+    CHITU_REQUIRE(logits && draft_logits && out && rows >= 0 && vocab > 0 && row_stride >= vocab && draft_row_stride >= vocab);
+    CHITU_REQUIRE(vocab <= (1 << 21));  // S < 2^61 keeps every product of the rule below 2^128
+    CHITU_REQUIRE(act_dtype >= 0 && act_dtype <= 2 && draft_act_dtype >= 0 && draft_act_dtype <= 2);
+    CHITU_REQUIRE(probs_mode == 0 || probs_mode == 1);
+    CHITU_REQUIRE(top_ks && top_ps && drafts && uniforms && (probs_mode || temperatures));
+    CHITU_REQUIRE(q_len >= 2 && q_len <= chitu::kVerifyMaxQ && rows % q_len == 0);
+    CHITU_REQUIRE(rows <= 0x7fffffff);
+    if (rows == 0) return CHITU_OK;
+    const int use_candidates = chitu::debug_option(chitu::kOptSampleRadix) > 0 ? 0 : 1;  // the rows without a draft: as chitu_hip_sample
+    hipLaunchKernelGGL(chitu::verify_sampled_rows_kernel, dim3((unsigned)rows), dim3(chitu::kSampleThreads), 0,
+                       (hipStream_t)stream, logits, row_stride, draft_logits, draft_row_stride, (int)vocab, temperatures, top_ks,
+                       top_ps, drafts, uniforms, (int)q_len, (int)probs_mode, out, accepted_out, row_tokens_out, use_candidates,
+                       (int)act_dtype, (int)draft_act_dtype);
+    // the sequence stage is chitu_hip_speculative_verify's
     const int bs = (int)(rows / q_len);
     hipLaunchKernelGGL(chitu::verify_sequences_kernel, dim3((unsigned)((bs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out, bs,
                        (int)q_len);

@@ -843,8 +843,11 @@ class DeepSeekV3Decoder(torch.nn.Module):
         """generate_speculative with generate()'s sampling parameters, LlamaDecoder.generate_speculative_sampled's contract on
         this decoder's decode_multi: one chitu_hip_speculative_verify call per round accepts a draft d with probability p(d)
         under the distribution p generate()'s sampler draws from, and replaces the first rejected draft by a draw from p without
-        d, renormalised.  Drafters are deterministic proposals (a drafter that samples its proposals would need its
-        probabilities in the rule: out of scope).  The output tokens are distributed as generate()'s but come from another
+        d, renormalised.  A drafter with propose(history, k) is a deterministic proposal; a sampling.ModelDrafter drafts on the
+        device with a draft model (e.g. a shallow stack of this decoder) and, with sample=True, draws its drafts from its own
+        distribution q under the request's parameters and hands over its logits: chitu_hip_speculative_verify_sampled accepts
+        with min(1, p(d) / q(d)) and replaces from max(p - q, 0), lossless for any q that d was drawn from (the drafter samples
+        without the frequency penalty).  The output tokens are distributed as generate()'s but come from another
         uniform stream.  With every top_k <= 1 the result is generate_speculative's."""
         from . import sampling
 

@@ -401,9 +401,12 @@ class LlamaDecoder(torch.nn.Module):
         renormalised; after draft_len accepted drafts a bonus token is drawn from p.  The frequency penalty of row t counts the
         response so far and the round's drafts before t.
 
-        Drafters are deterministic proposals: drafter.propose(history, draft_len) names tokens, and the rule above is rejection
-        sampling against a point mass.  A drafter that samples its proposals would have to hand over their probabilities
-        (accept with min(1, p / q), replace from max(p - q, 0)): out of scope here.  The output tokens are distributed as
+        A drafter with propose(history, draft_len) names tokens: a deterministic proposal, and the rule above is rejection
+        sampling against a point mass.  A sampling.ModelDrafter drafts on the device with a draft model and, with sample=True,
+        draws each draft from the draft model's distribution q under the request's own temperature / top_k / top_p (without the
+        frequency penalty) and hands over its logits: ONE chitu_hip_speculative_verify_sampled call accepts d with min(1, p(d) /
+        q(d)) and replaces a rejected draft by a draw from max(p - q, 0), renormalised -- lossless for any q, provided q is what
+        d was drawn from.  The output tokens are distributed as
         generate()'s with the same parameters, but they come from another uniform stream: the same generator seed does not
         give generate()'s tokens.  With every top_k <= 1 the result is generate_speculative's.
 

@@ -17,7 +17,9 @@ distribution but another stream).
 
 No reference counterpart: speculative decoding.  `generate_speculative_greedy` / `generate_speculative_sampled` are the
 draft-and-verify loops of the decoders' generate_speculative / generate_speculative_sampled; the sampled one judges the drafts on the
-device with ONE `chitu_hip_speculative_verify` call per round (`speculative_verify`; rule and proof in DESIGN 3.9).
+device with ONE `chitu_hip_speculative_verify` call per round (`speculative_verify`; rule and proof in DESIGN 3.9).  `ModelDrafter`
+drafts with a second, smaller decoder of this package on the device; where it samples its drafts the round is judged by
+`chitu_hip_speculative_verify_sampled` (`speculative_verify_sampled`: accept with min(1, p / q), replace from max(p - q, 0)).
 """
 
 from typing import List, Optional, Sequence, Tuple
@@ -35,7 +37,9 @@ __all__ = [
     "sample_tokens",
     "DeviceSampler",
     "NgramDrafter",
+    "ModelDrafter",
     "speculative_verify",
+    "speculative_verify_sampled",
     "generate_speculative_greedy",
     "generate_speculative_sampled",
 ]
@@ -277,6 +281,125 @@ def speculative_verify(logits, drafts, T, temperatures, top_ks, top_ps, uniforms
     return (out, accepted, row_tokens) if return_rows else out
 
 
+def speculative_verify_sampled(logits, draft_logits, drafts, T, temperatures, top_ks, top_ps, uniforms=None, generator=None,
+                               probs_mode=False, return_rows=False):
+    """speculative_verify for drafts that were SAMPLED (chitu_hip_speculative_verify_sampled; new: the reference has no speculative
+    path): draft_logits [bs * T, vocab] (or [bs, T, vocab]; any float dtype, its own row stride) holds, in row (b, t), the draft
+    model's logits that drafts[b * T + t] was drawn from under the row's own temperature / top_k / top_p -- the parameters apply to
+    both rows of a pair.  With p the target row's distribution and q the draft row's, a draft d is accepted with probability
+    min(1, p(d) / q(d)) and the first rejected row emits a draw from max(p - q, 0), renormalised: every emitted token is distributed
+    as p, whatever q is, provided q is what d was drawn from.  The draft row of each sequence's last row (drafts -1) is never read.
+    Everything else -- uniforms [bs * T, 2], the result [bs, T + 1], return_rows -- as speculative_verify."""
+    require_cuda(logits, draft_logits)
+    x2, rows, vocab = _rows(logits)
+    q2, q_rows, q_vocab = _rows(draft_logits)
+    T = int(T)
+    if T < 2 or rows % T:
+        raise ValueError(f"speculative_verify_sampled: {rows} rows are not sequences of T={T} >= 2 rows")
+    if (q_rows, q_vocab) != (rows, vocab):
+        raise ValueError(f"speculative_verify_sampled: draft_logits [{q_rows}, {q_vocab}] against logits [{rows}, {vocab}]")
+    dev = logits.device
+    d = _per_row(drafts, rows, torch.int32, dev)
+    if uniforms is None:
+        u = torch.rand(rows, 2, dtype=torch.float32, device=dev, generator=generator)
+    else:
+        u = _per_row(uniforms, rows * 2, torch.float32, dev)
+    temps = None if probs_mode and temperatures is None else _per_row(temperatures, rows, torch.float32, dev)
+    ks, ps = _per_row(top_ks, rows, torch.int32, dev), _per_row(top_ps, rows, torch.float32, dev)
+    out = torch.empty(rows // T, T + 1, dtype=torch.int64, device=dev)
+    accepted = row_tokens = None
+    if return_rows:
+        accepted = torch.empty(rows, dtype=torch.int32, device=dev)
+        row_tokens = torch.empty(rows, dtype=torch.int64, device=dev)
+    check(_lib.lib().chitu_hip_speculative_verify_sampled(
+        ptr(x2), float_dtype_code(x2.dtype), i64(x2.stride(0)), ptr(q2), float_dtype_code(q2.dtype), i64(q2.stride(0)), i64(rows),
+        i32(vocab), ptr(temps), ptr(ks), ptr(ps), ptr(d), ptr(u), i32(T), i32(1 if probs_mode else 0), ptr(out), ptr(accepted),
+        ptr(row_tokens), stream_ptr()), "speculative_verify_sampled")
+    return (out, accepted, row_tokens) if return_rows else out
+
+
+class ModelDrafter:
+    """Drafts from a draft MODEL: any decoder of this package (prefill, decode, cache, device, args.vocab_size) with the target's
+    vocabulary, built by the caller with a paged cache of its own -- Llama-3.2-3B for Llama-3-8B, a shallow stack for a deep one.
+    Both speculative loops take it (they look for `draft`; a drafter with only propose(history, k) takes the host path):
+
+      start(prompts, req_ids)   prefills the draft model (the logits are dropped).
+      draft(last_tokens, req_ids, draft_len, temperatures, top_ks, top_ps, generator) -> (drafts, draft_logits)
+                                draft_len + 1 graph-replayed decode steps from last_tokens [n] int64 on the device.  Step s's token
+                                is picked on the device -- arg-max, or with sample=True and top_ks given
+                                top_k_top_p_sampling_from_logits under the requests' parameters ([n] each) with uniforms from
+                                `generator` -- and feeds step s + 1 without visiting the host, as generate() does.  drafts
+                                [n, draft_len] int64; draft_logits [n, draft_len + 1, vocab] f32 where the drafts were sampled
+                                (each draft's logits, copied out of the graph's static output before the next replay; the last
+                                row is unused and left unwritten), else None -- arg-max drafts keep no logits.
+      settle(req_ids, kept)     after the verify step emitted kept[b] tokens: the draft cache goes back to the target's length.
+                                Pairs with draft(): it gives back the rows that the request's LAST draft() appended, less
+                                kept[b], and raises for a request that has no draft() since its last settle().
+      retire(req_id)            frees the request's pages.
+
+    The step after the last draft is ALWAYS run: it appends the last draft's row, which a request that accepts every draft needs
+    and would otherwise lack, so after a round every request's draft cache holds last token + all drafts and settle() is one
+    rollback of draft_len + 1 - kept[b] rows -- no second, ragged catch-up step with a batch (and a captured graph) of its own, and
+    nothing in the round waits for the verify result."""
+
+    def __init__(self, model, sample=True):
+        for name in ("prefill", "decode", "cache", "device", "args"):
+            if not hasattr(model, name):
+                raise TypeError(f"ModelDrafter: the draft model has no {name!r}")
+        self.model, self.sample = model, bool(sample)
+        self._appended = {}  # req_id -> rows its last draft() appended and no settle() has accounted for yet
+
+    def check_target(self, target):
+        """ValueError unless the draft model can draft for `target` (the loops call this before anything is prefilled)"""
+        if int(self.model.args.vocab_size) != int(target.args.vocab_size):
+            raise ValueError(f"ModelDrafter: the draft model's vocabulary ({self.model.args.vocab_size}) differs from the "
+                             f"target's ({target.args.vocab_size})")
+        if self.model.cache is target.cache:
+            raise ValueError("ModelDrafter: the draft model shares the target's cache object; it needs a paged cache of its own")
+
+    def start(self, prompts, req_ids):
+        self.model.prefill(prompts, list(req_ids))
+
+    def draft(self, last_tokens, req_ids, draft_len, temperatures=None, top_ks=None, top_ps=None, generator=None, use_graph=True):
+        m, ids = self.model, list(req_ids)
+        n = len(ids)
+        assert last_tokens.dtype == torch.int64 and tuple(last_tokens.shape) == (n,)
+        sampled = self.sample and top_ks is not None
+        drafts = torch.empty(n, draft_len, dtype=torch.int64, device=m.device)
+        kept_logits = torch.empty(n, draft_len + 1, int(m.args.vocab_size), dtype=torch.float32, device=m.device) if sampled else None
+        tok = last_tokens
+        for r in ids:
+            if r in self._appended:
+                raise RuntimeError(f"ModelDrafter.draft: request {r!r} has a draft() that no settle() followed")
+            self._appended[r] = draft_len + 1  # settle() gives back all but the kept ones
+        for s in range(draft_len + 1):
+            m.cache.prepare_cache_decode(ids)
+            m.cache.prepare_block_table_for_decode(ids)
+            logits = m.decode(tok, use_graph=use_graph)
+            m.cache.finalize_cache_single_decode(ids)
+            if kept_logits is not None and s < draft_len:  # the row after the last draft judges nothing
+                kept_logits[:, s].copy_(logits)
+            if s < draft_len:
+                if sampled:
+                    tok = top_k_top_p_sampling_from_logits(logits, temperatures, top_ks, top_ps, generator=generator)
+                else:
+                    tok = argmax(logits)
+                drafts[:, s] = tok
+        return drafts, kept_logits
+
+    def settle(self, req_ids, kept):
+        """the requests' last draft() appended draft_len + 1 rows each, the target kept kept[b] (1 .. draft_len + 1) of them"""
+        ids = list(req_ids)
+        missing = [r for r in ids if r not in self._appended]
+        if missing:
+            raise RuntimeError(f"ModelDrafter.settle: no draft() to settle for {missing!r}")
+        self.model.cache.rollback(ids, [self._appended.pop(r) - int(k) for r, k in zip(ids, kept)])
+
+    def retire(self, req_id):
+        self._appended.pop(req_id, None)
+        self.model.cache.finalize_cache_all_decode(req_id)
+
+
 def _check_draft_len(draft_len, max_q):
     if not 1 <= draft_len <= max_q - 1:
         raise ValueError(f"draft_len={draft_len}: a verify step holds the last token and 1 .. {max_q - 1} drafts")
@@ -309,17 +432,141 @@ def _finish_speculative(model, out, stats, max_new_tokens):
     return torch.tensor([o[:max_new_tokens] for o in out], dtype=torch.int64, device=model.device)
 
 
+def _start_model_drafter(model, drafter, prompts, req_ids):
+    if hasattr(drafter, "check_target"):
+        drafter.check_target(model)
+    drafter.start(prompts, req_ids)
+
+
+def _retire_finished_drafted(model, drafter, req_ids, out, live, last, max_new_tokens):
+    """_retire_finished for both models; returns `last` (the live requests' last tokens, on the device) without the rows that left"""
+    gone = [i for i in live if len(out[i]) >= max_new_tokens]
+    if not gone:
+        return last
+    keep = [j for j, i in enumerate(live) if i not in gone]
+    for i in gone:
+        model.cache.finalize_cache_all_decode(req_ids[i])
+        drafter.retire(req_ids[i])
+        live.remove(i)
+    return last[torch.tensor(keep, dtype=torch.int64, device=last.device)] if keep else last[:0]
+
+
+def _generate_speculative_greedy_drafted(model, prompts, max_new_tokens, drafter, draft_len, req_ids, use_graph):
+    """generate_speculative_greedy with a drafter that drafts on the device (ModelDrafter's protocol): arg-max drafts, today's
+    comparison.  The step tensor is assembled on the device and the next round's last tokens are gathered there; one device ->
+    host copy per round carries the drafts and the arg-maxes."""
+    n_req, T = len(prompts), draft_len + 1
+    _start_model_drafter(model, drafter, prompts, req_ids)
+    last = argmax(model.prefill(prompts, req_ids))
+    out = [[t] for t in last.tolist()]
+    stats = {"steps": 0, "accepted": 0, "drafted": 0}
+    live = list(range(n_req))
+    if max_new_tokens <= 1:
+        live = []
+        for r in req_ids:
+            model.cache.finalize_cache_all_decode(r)
+            drafter.retire(r)
+    while live:
+        ids = [req_ids[i] for i in live]
+        drafts, _ = drafter.draft(last, ids, draft_len, use_graph=use_graph)
+        model.cache.prepare_block_table_for_decode_multi(ids, T)
+        logits = model.decode_multi(torch.cat([last.view(-1, 1), drafts], dim=1), use_graph=use_graph)
+        best = argmax(logits.view(len(live) * T, -1)).view(len(live), T)
+        n_ok = (drafts == best[:, :draft_len]).to(torch.int64).cumprod(dim=1).sum(dim=1, keepdim=True)
+        last = best.gather(1, n_ok).view(-1)  # the bonus token: the next round's last token, never off the device
+        both = torch.cat([drafts, best], dim=1).tolist()
+        kept = []
+        for i, row in zip(live, both):
+            d, a = row[:draft_len], row[draft_len:]
+            k = 0
+            while k < draft_len and d[k] == a[k]:
+                k += 1
+            out[i].extend(d[:k] + [a[k]])
+            kept.append(k + 1)
+            stats["accepted"] += k
+            stats["drafted"] += draft_len
+        stats["steps"] += 1
+        model.cache.finalize_cache_multi_decode(ids, kept)
+        drafter.settle(ids, kept)
+        last = _retire_finished_drafted(model, drafter, req_ids, out, live, last, max_new_tokens)
+    return _finish_speculative(model, out, stats, max_new_tokens)
+
+
+def _generate_speculative_sampled_drafted(model, prompts, max_new_tokens, drafter, draft_len, temps, ks, ps, pens, generator, req_ids,
+                                          use_graph):
+    """generate_speculative_sampled with a drafter that drafts on the device (ModelDrafter's protocol).  The drafter draws each
+    draft from ITS distribution q under the request's temperature / top_k / top_p (without the frequency penalty: the rule is
+    lossless for any q, provided q is what d was drawn from) and hands over the logits; speculative_verify_sampled judges the
+    round.  A drafter that does not sample (sample=False, or every top_k <= 1) proposes arg-maxes: a point mass, judged by
+    speculative_verify.  Without a penalty the round's only device -> host copy is the [bs, T + 1] result; with one, the drafts
+    travel too (the penalty of row t counts them, as with a host drafter)."""
+    n_req, T = len(prompts), draft_len + 1
+    dev = model.device
+    greedy = all(k <= 1 for k in ks)
+    penalise = any(p > 0 for p in pens)
+    _start_model_drafter(model, drafter, prompts, req_ids)
+    last = sample_tokens(model.prefill(prompts, req_ids), temps, ks, ps, generator=generator)
+    out = [[t] for t in last.tolist()]
+    stats = {"steps": 0, "accepted": 0, "drafted": 0}
+    live = list(range(n_req))
+    if max_new_tokens <= 1:
+        live = []
+        for r in req_ids:
+            model.cache.finalize_cache_all_decode(r)
+            drafter.retire(r)
+    params_of = None
+    no_draft = None
+    while live:
+        ids = [req_ids[i] for i in live]
+        n = len(live)
+        if params_of != live:  # the parameters on the device, per request (the drafter's) and per row (the verify launch's)
+            params_of = list(live)
+            req_params = [_per_row([v[i] for i in live], n, dt, dev) for v, dt in ((temps, torch.float32), (ks, torch.int32), (ps, torch.float32))]
+            dev_params = [v.repeat_interleave(T) for v in req_params]
+            no_draft = torch.full((n, 1), -1, dtype=torch.int64, device=dev)
+        if greedy:
+            drafts, draft_logits = drafter.draft(last, ids, draft_len, use_graph=use_graph)
+        else:
+            drafts, draft_logits = drafter.draft(last, ids, draft_len, *req_params, generator=generator, use_graph=use_graph)
+        model.cache.prepare_block_table_for_decode_multi(ids, T)
+        logits = model.decode_multi(torch.cat([last.view(-1, 1), drafts], dim=1), use_graph=use_graph).view(n * T, -1)
+        if penalise:
+            host_drafts = drafts.tolist()
+            apply_frequency_penalty(logits, [out[i] + d[:t] for i, d in zip(live, host_drafts) for t in range(T)],
+                                    [pens[i] for i in live for _ in range(T)])
+        row_drafts = torch.cat([drafts, no_draft], dim=1).to(torch.int32).view(-1)
+        if draft_logits is not None and not greedy:
+            res = speculative_verify_sampled(logits, draft_logits.view(n * T, -1), row_drafts, T, *dev_params, generator=generator)
+        else:
+            res = speculative_verify(logits, row_drafts, T, *dev_params, generator=generator)
+        last = res.gather(1, res[:, :1]).view(-1)  # column n_emitted holds the last emitted token
+        kept = []
+        for i, row in zip(live, res.tolist()):
+            out[i].extend(row[1 : 1 + row[0]])
+            kept.append(row[0])
+            stats["accepted"] += row[0] - 1
+            stats["drafted"] += draft_len
+        stats["steps"] += 1
+        model.cache.finalize_cache_multi_decode(ids, kept)
+        drafter.settle(ids, kept)
+        last = _retire_finished_drafted(model, drafter, req_ids, out, live, last, max_new_tokens)
+    return _finish_speculative(model, out, stats, max_new_tokens)
+
+
 def generate_speculative_greedy(model, prompts, max_new_tokens, drafter, draft_len, max_q, req_ids=None, use_graph=True,
                                 sampling_args=()):
     """The draft-and-verify loop of LlamaDecoder / DeepSeekV3Decoder.generate_speculative (their docstrings state the contract):
     model-independent, it needs model.prefill, model.decode_multi, model.cache and model.device, and leaves
-    model.speculative_stats.  max_q: the most tokens a verify step of the model holds (the last token + max_q - 1 drafts)."""
+    model.speculative_stats.  max_q: the most tokens a verify step of the model holds (the last token + max_q - 1 drafts).
+    A drafter with `draft` (ModelDrafter) drafts arg-maxes on the device; one with only propose(history, k) takes the host path."""
     if any(a is not None for a in sampling_args):
         raise NotImplementedError("generate_speculative is greedy (it accepts a draft iff draft == argmax): "
                                   "generate_speculative_sampled takes temperatures, top_ks, top_ps and frequency_penalties")
     _check_draft_len(draft_len, max_q)
     n_req = len(prompts)
     req_ids = [f"gen{i}" for i in range(n_req)] if req_ids is None else list(req_ids)
+    if hasattr(drafter, "draft"):  # a drafter that drafts on the device (ModelDrafter)
+        return _generate_speculative_greedy_drafted(model, prompts, max_new_tokens, drafter, draft_len, req_ids, use_graph)
     T = draft_len + 1
     first = argmax(model.prefill(prompts, req_ids)).tolist()
     out = [[t] for t in first]
@@ -358,7 +605,8 @@ def generate_speculative_sampled(model, prompts, max_new_tokens, drafter, draft_
     any penalty > 0, row (b, t) of the verify logits is penalised with response[b] + drafts[b][:t] (what the response would be if
     the drafts before t are accepted -- and row t only counts if they are) in one launch over the bs * T rows; then ONE
     speculative_verify call and ONE copy of its [bs, T + 1] result to the host.  If every top_k <= 1 the rows are greedy rows
-    of the same kernel (accepted iff draft == argmax): generate_speculative_greedy's tokens."""
+    of the same kernel (accepted iff draft == argmax): generate_speculative_greedy's tokens.  A drafter with `draft` (ModelDrafter)
+    takes _generate_speculative_sampled_drafted's rounds instead: sampled drafts, judged with their probabilities."""
     _check_draft_len(draft_len, max_q)
     n_req = len(prompts)
     req_ids = [f"gen{i}" for i in range(n_req)] if req_ids is None else list(req_ids)
@@ -372,6 +620,9 @@ def generate_speculative_sampled(model, prompts, max_new_tokens, drafter, draft_
 
     temps, ps, pens = as_list(temperatures, 1.0), as_list(top_ps, 1.0), as_list(frequency_penalties, 0.0)
     assert len(ks) == len(temps) == len(ps) == len(pens) == n_req
+    if hasattr(drafter, "draft"):  # a drafter that drafts on the device (ModelDrafter)
+        return _generate_speculative_sampled_drafted(model, prompts, max_new_tokens, drafter, draft_len, temps, ks, ps, pens, generator,
+                                                     req_ids, use_graph)
     penalise = any(p > 0 for p in pens)
     first = sample_tokens(model.prefill(prompts, req_ids), temps, ks, ps, generator=generator).tolist()
     out = [[t] for t in first]

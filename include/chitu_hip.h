@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 11  /* 11: + chitu_hip_speculative_verify (draft verification of speculative decoding with sampling, next to chitu_hip_sample), additive only.  10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 12  /* 12: + chitu_hip_speculative_verify_sampled (verification against a draft that was itself sampled: accept with min(1, p / q), replace from max(p - q, 0), in 128-bit integers), additive only.  11: + chitu_hip_speculative_verify (draft verification of speculative decoding with sampling, next to chitu_hip_sample), additive only.  10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -957,6 +957,25 @@ int chitu_hip_speculative_verify(const void* logits, int act_dtype, int64_t row_
                                  const float* temperatures, const int32_t* top_ks, const float* top_ps,
                                  const int32_t* drafts, const float* uniforms, int32_t q_len, int32_t probs_mode,
                                  int64_t* out, int32_t* accepted_out, int64_t* row_tokens_out, void* stream);
+/*   chitu_hip_speculative_verify_sampled  new: no reference counterpart.  The same verification for a draft d that was DRAWN from a
+ *     draft model's distribution q: accepted with probability min(1, p(d) / q(d)); a rejected row emits a draw from max(p - q, 0),
+ *     renormalised, so every emitted token is distributed as p for ANY q, provided q is what d was drawn from.  Arguments as
+ *     chitu_hip_speculative_verify, plus draft_logits [rows, vocab] with its own draft_act_dtype and draft_row_stride, indexed by
+ *     the same row b * q_len + t; temperatures / top_ks / top_ps / probs_mode apply to both rows of a pair (the drafter samples
+ *     under the request's parameters).  The draft row of a row without a draft (drafts < 0, each sequence's last) is never read
+ *     and may hold anything.  vocab <= 2^21.  In integers, with K_p, w_i, S_p the kept set, weights and sum of the target row as
+ *     above, K_q, v_i, S_q the same of the draft row and U(u) = min(floor(u * 2^24), 2^24 - 1): top_k == 1, S_p == 0 or S_q == 0
+ *     -> accepted iff d == arg-max of the target row, token = that arg-max; d < 0 -> not accepted, token = chitu_hip_sample's
+ *     for u_alt on the target row; else with w_d, v_d the kept weights of d (0 if not kept or >= vocab): accepted iff
+ *     U(u_acc) * v_d * S_p < 2^24 * w_d * S_q with token = d, otherwise r_i = max(0, w_i * S_q - v_i * S_p), R = sum r_i and token
+ *     = inverse CDF over r in index order at floor(U(u_alt) * R / 2^24) (R == 0, which no rejection of a d drawn from q gives:
+ *     the arg-max).  All products in unsigned 128-bit integers.  out / accepted_out / row_tokens_out and the two launches as
+ *     chitu_hip_speculative_verify. */
+int chitu_hip_speculative_verify_sampled(const void* logits, int act_dtype, int64_t row_stride, const void* draft_logits,
+                                         int draft_act_dtype, int64_t draft_row_stride, int64_t rows, int32_t vocab,
+                                         const float* temperatures, const int32_t* top_ks, const float* top_ps,
+                                         const int32_t* drafts, const float* uniforms, int32_t q_len, int32_t probs_mode,
+                                         int64_t* out, int32_t* accepted_out, int64_t* row_tokens_out, void* stream);
 
 /* ---- in-graph tensor-parallel collectives over xGMI (csrc/comm.hip) --------------------------------
  * Replace the NCCL calls of the reference's decode step -- dist.all_reduce after every RowParallelLinear

@@ -10,6 +10,7 @@ median, minimum and maximum over `--replays` rounds are printed and written as J
                     just does not count): no row draws -- the cost of an accepted row
   sample            chitu_hip_sample over the same 64 rows
   sample_parent     the same launch from another build of the library (--parent-lib), e.g. the parent commit's
+  verify_accepted_parent / verify_rejected_parent   the two verify calls from that build
 
 usage: python tools/spec_verify_timing.py [--parent-lib PATH] [--radix] [--out profiles/spec_verify_timing.json]
 """
@@ -67,6 +68,16 @@ def main():
     }
     if parent is not None:
         launches["sample_parent"] = lambda: sample_with(parent, out_par)
+        par_out = {k: (torch.zeros(bs, T + 1, dtype=torch.int64, device="cuda"), torch.zeros(rows, dtype=torch.int32, device="cuda"),
+                       torch.zeros(rows, dtype=torch.int64, device="cuda")) for k in ("acc", "rej")}
+
+        def verify_parent(key, drafts):
+            o, acc_o, tok_o = par_out[key]
+            _lib.check(parent.chitu_hip_speculative_verify(ptr(x), 2, i64(vocab), i64(rows), i32(vocab), ptr(temps), ptr(ks), ptr(ps), ptr(drafts),
+                                                           ptr(u2), i32(T), i32(0), ptr(o), ptr(acc_o), ptr(tok_o), stream_ptr()), "verify (parent)")
+
+        launches["verify_accepted_parent"] = lambda: verify_parent("acc", best)
+        launches["verify_rejected_parent"] = lambda: verify_parent("rej", worst)
 
     if a.radix:
         _lib.check(_lib.lib().chitu_hip_debug_option(i32(_lib.DEBUG_OPTIONS["sample_radix"]), i32(1)), "debug_option")
@@ -89,6 +100,9 @@ def main():
     assert int(acc[0][:, 0].min()) == T and int(rej[0][:, 0].max()) == 1 and int(results["all"][1].min()) == 1
     if parent is not None:
         assert torch.equal(out_tok, out_par), "chitu_hip_sample differs from the parent build's"
+        for key in ("acc", "rej"):
+            for mine, theirs in zip(results[key], par_out[key]):
+                assert torch.equal(mine, theirs), "chitu_hip_speculative_verify differs from the parent build's"
     assert torch.equal(rej[2], out_tok), "a rejected draft outside the kept set leaves chitu_hip_sample's draw for u_alt"
 
     times = {name: [] for name in graphs}
@@ -105,7 +119,7 @@ def main():
            "device": torch.cuda.get_device_name(0), "us_per_launch": {}}
     for name, ts in times.items():
         doc["us_per_launch"][name] = {"median": round(statistics.median(ts), 2), "min": round(min(ts), 2), "max": round(max(ts), 2)}
-        print(f"{name:16s} median {statistics.median(ts):8.2f} us  (min {min(ts):.2f}, max {max(ts):.2f})")
+        print(f"{name:24s} median {statistics.median(ts):8.2f} us  (min {min(ts):.2f}, max {max(ts):.2f})")
     print(json.dumps(doc))
     if a.out:
         with open(a.out, "w") as f:
