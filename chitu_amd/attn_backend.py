@@ -535,6 +535,53 @@ class HipAttnBackend(AttnBackend):
                                                 softmax_scale=softmax_scale).view(t1 - t0, Hq, D)
         return out
 
+    # ------------------------------------------------------------------ GQA / MHA continued prefill over the paged cache
+    def attn_varlen_with_kvcache(self, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, max_seqlen_q, causal=True,
+                                 window_size=(-1, -1), softcap=0.0, softmax_scale=None):
+        """The ragged form of attn_with_kvcache (no reference counterpart: attn_varlen_func's separate cu_seqlens_q with its keys
+        in the pages, attn_with_kvcache at any seqlen_q): continued and chunked prefill.
+
+        q [T, Hq, 128] bf16, sequence s owning rows cu_seqlens_q[s] .. cu_seqlens_q[s + 1]; k_cache / v_cache
+        [pages, page_size, Hkv, 128] bf16 with those rows' K and V already written; cache_seqlens [n_seq] int32 counts ALL keys
+        of a sequence, the new rows included; block_table [n_seq, max_pages] int32; max_seqlen_q bounds the launch.  Query i of
+        sequence s sits at position cache_seqlens[s] - n_s + i and sees the keys up to itself (the causal mask aligned to the bottom
+        right), within window_size = (W, 0) the last W + 1 of them; softcap as in attn_with_kvcache.  Returns [T, Hq, 128].
+        One launch of chitu_hip_gqa_prefill_paged (csrc/gqa_prefill_flash.hip, kPaged): the pages are read once per 128 / (Hq / Hkv)
+        query tokens.  An fp8 cache raises NotImplementedError (the LDS-DMA cannot widen 144-byte rows), as does a mask that is
+        not causal."""
+        if is_fp8_gqa_cache(k_cache) or is_fp8_gqa_cache(v_cache):
+            raise NotImplementedError("attn_varlen_with_kvcache reads bf16 K / V pages; the fp8 K / V cache is not implemented")
+        window_left, softcap = window_and_cap(window_size, softcap, causal)
+        if not causal and int(window_size[1]) != 0:
+            raise NotImplementedError(f"causal=False with window_size={tuple(window_size)}: only the causal mask (causal=True, or a "
+                                      "window whose right side is 0) is implemented")
+        require_cuda(q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table)
+        assert q.dim() == 3 and q.dtype == torch.bfloat16 and k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16
+        assert k_cache.dim() == 4 and k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape
+        assert cache_seqlens.dtype == torch.int32 and cache_seqlens.is_contiguous()
+        assert block_table.dtype == torch.int32 and block_table.dim() == 2 and block_table.stride(1) == 1
+        T, Hq, D = q.shape
+        Hkv = k_cache.shape[2]
+        n_seq = cache_seqlens.numel()
+        assert cu_seqlens_q.numel() == n_seq + 1 and block_table.shape[0] == n_seq and k_cache.shape[3] == D
+        if T == 0:
+            return q.new_empty(0, Hq, D)
+        if softmax_scale is None:
+            softmax_scale = D ** -0.5
+        if not (q.stride(-1) == 1 and q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0):
+            q = q.contiguous()
+        cu32 = cu_seqlens_q.to(device=q.device, dtype=torch.int32).contiguous()
+        out = torch.empty(T, Hq, D, dtype=torch.bfloat16, device=q.device)
+        check(
+            _lib.lib().chitu_hip_gqa_prefill_paged(
+                ptr(q), i64(q.stride(0)), i64(q.stride(1)), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
+                i32(Hkv), ptr(block_table), i32(block_table.stride(0)), ptr(cu32), ptr(cache_seqlens), i32(n_seq),
+                i32(int(max_seqlen_q)), f32(softmax_scale), ptr(out), i32(Hq), i32(D), i32(window_left), f32(softcap), stream_ptr(),
+            ),
+            "gqa_prefill_paged",
+        )
+        return out
+
     # ------------------------------------------------------------------ non-MLA (GQA / MHA) paged decode
     def attn_with_kvcache(
         self,

@@ -360,6 +360,80 @@ class PagedKVCacheManager:
                 self.free_blocks.append(self.block_table[req_id].pop())
                 self._table_rows = None
 
+    # ---- continued / chunked prefill: n new tokens per request behind rows that are already cached
+    def prepare_cache_prefill_continue(self, req_ids, varlen):
+        """Make room for the varlen.cpu_lens[b] tokens a continued prefill appends to request b (already cached, any length) and
+        stage what the step reads:
+          get_continue_position_ids()        [T] int64  absolute position of every new token: its RoPE row
+          get_gpu_continue_seq_lens_incl()   [n] int32  the old length + the new tokens: the keys the attention sees
+          get_gpu_continue_block_table()     [n, max_blocks] int32
+        and, for finalize_cache_bylayer_prefill_continue, the flat page row of every new token.  Every request's capacity and
+        the free pages are checked before a page is taken from any (prepare_block_table_for_decode_multi's rule); each block
+        table then grows to ceil((len + n) / block_size) pages -- finalize_cache_all_prefill_continue advances the lengths, so
+        the single-token step's invariant holds again."""
+        req_ids = list(req_ids)
+        counts = [int(c) for c in varlen.cpu_lens]
+        assert len(counts) == len(req_ids) and len(set(req_ids)) == len(req_ids)
+        need = 0
+        for req_id, c in zip(req_ids, counts):
+            if req_id not in self.seq_lens:
+                raise KeyError(f"request {req_id!r} is not cached: a continued prefill extends a sequence that prefill registered")
+            assert c >= 1, f"request {req_id!r}: a continued prefill needs at least one new token"
+            if self.seq_lens[req_id] + c > self.max_blocks_per_req * self.block_size:
+                raise Exception(f"request {req_id!r}: {self.seq_lens[req_id]} + {c} tokens do not fit its block table")
+            need += -(-(self.seq_lens[req_id] + c) // self.block_size) - len(self.block_table[req_id])
+        if need > len(self.free_blocks):
+            raise Exception(f"{need} more pages for {sum(counts)} tokens do not fit the {len(self.free_blocks)} free pages")
+        rows, pos = [], []
+        for req_id, c in zip(req_ids, counts):
+            L0 = self.seq_lens[req_id]
+            while len(self.block_table[req_id]) * self.block_size < L0 + c:
+                self.block_table[req_id].append(self.get_free_block())
+                self._table_rows = None  # the single-token step's device table no longer shows this request's pages
+            t = torch.arange(L0, L0 + c, dtype=torch.int64)
+            blocks = torch.tensor(self.block_table[req_id], dtype=torch.int64)
+            rows.append(blocks[t // self.block_size] * self.block_size + t % self.block_size)
+            pos.append(t)
+        table = torch.zeros(len(req_ids), self.max_blocks_per_req, dtype=torch.int32)
+        for b, req_id in enumerate(req_ids):
+            table[b, : len(self.block_table[req_id])] = torch.tensor(self.block_table[req_id], dtype=torch.int32)
+        lens = torch.tensor([self.seq_lens[r] + c for r, c in zip(req_ids, counts)], dtype=torch.int32)
+        dev = self.device
+        self._continue = dict(req_ids=req_ids, counts=counts, rows=torch.cat(rows).to(dev), positions=torch.cat(pos).to(dev),
+                              table=table.to(dev), lens=lens.to(dev))
+
+    def get_continue_position_ids(self):
+        return self._continue["positions"]
+
+    def get_gpu_continue_seq_lens_incl(self):
+        return self._continue["lens"]
+
+    def get_gpu_continue_block_table(self):
+        return self._continue["table"]
+
+    def finalize_cache_bylayer_prefill_continue(self, xk, xv, layer_id):
+        """Write the new tokens' rows of one layer into their pages: one scatter (index_copy_) per cache, as
+        finalize_cache_bylayer_prefill."""
+        li = layer_id - self.begin_layer_id
+        rows = self._continue["rows"]
+        if self.kv_shape_per_sample is not None:
+            c = self.paged_kv_cache[li]
+            c.view(-1, *c.shape[2:]).index_copy_(0, rows, xk[: rows.numel()].to(c.dtype))
+        else:
+            ck, cv = self.paged_k_cache[li], self.paged_v_cache[li]
+            ck.view(-1, *ck.shape[2:]).index_copy_(0, rows, xk[: rows.numel()].to(ck.dtype))
+            cv.view(-1, *cv.shape[2:]).index_copy_(0, rows, xv[: rows.numel()].to(cv.dtype))
+
+    def finalize_cache_all_prefill_continue(self, req_ids):
+        """The continued prefill has run: the requests' lengths advance by their new tokens."""
+        c = self._continue
+        assert list(req_ids) == c["req_ids"]
+        for req_id, n in zip(c["req_ids"], c["counts"]):
+            self.seq_lens[req_id] += n
+        self._continue = None
+        self.curr_varlens = None
+        self.curr_req_ids = None
+
     def finalize_cache_single_decode(self, req_ids):
         for req_id in req_ids:
             self.seq_lens[req_id] = self.seq_lens[req_id] + 1

@@ -148,7 +148,10 @@ class LlamaAttention(torch.nn.Module):
 
     def prefill_forward(self, x, cos, sin, varlens):
         """models/model.py:104-132: projections on all T prompt tokens, RoPE, page writes by the cache
-        manager (cache_manager.py:93-142), causal GQA through attn_backend.attn_varlen_func."""
+        manager (cache_manager.py:93-142), causal GQA through attn_backend.attn_varlen_func.  varlens.continued (set by
+        LlamaDecoder.prefill_continue): the rows extend cached sequences -- prefill_forward_paged."""
+        if getattr(varlens, "continued", False):
+            return self.prefill_forward_paged(x, cos, sin, varlens)
         T = x.shape[0]
         qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
         q, k = ops.apply_rotary_pos_emb(qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv], cos, sin, rotary_type=self.rotary_type)
@@ -162,6 +165,22 @@ class LlamaAttention(torch.nn.Module):
             self.cache.finalize_cache_bylayer_prefill(k, v, self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
         o = self.attn_backend.attn_varlen_func(q, k, v, varlens.prefix_lens, varlens.prefix_lens, varlens.max_len,
                                                varlens.max_len, causal=True, window_size=self.window_size, softcap=self.softcap)
+        return ops.bf16_linear(o.reshape(T, self.hq * self.hd), self.wo)
+
+    def prefill_forward_paged(self, x, cos, sin, varlens):
+        """prefill_forward for tokens behind rows that are already cached (PagedKVCacheManager.prepare_cache_prefill_continue has
+        run): projections, RoPE at the absolute positions (cos / sin rows), the new K / V rows scattered into their pages, then ONE
+        attention call over the pages -- every query sees the cached prefix and the new rows up to itself."""
+        assert not self.fp8_kv, "continued prefill reads bf16 K / V pages"
+        T = x.shape[0]
+        qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
+        q, k = ops.apply_rotary_pos_emb(qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv], cos, sin, rotary_type=self.rotary_type)
+        v = qkv[:, self.hq + self.hkv :].contiguous()
+        self.cache.finalize_cache_bylayer_prefill_continue(k, v, self.layer_id)
+        k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
+        o = self.attn_backend.attn_varlen_with_kvcache(
+            q, k_cache, v_cache, varlens.prefix_lens, self.cache.get_gpu_continue_seq_lens_incl(),
+            self.cache.get_gpu_continue_block_table(), varlens.max_len, causal=True, window_size=self.window_size, softcap=self.softcap)
         return ops.bf16_linear(o.reshape(T, self.hq * self.hd), self.wo)
 
 
@@ -254,10 +273,29 @@ class LlamaDecoder(torch.nn.Module):
         return tp.all_reduce(torch.where(mask.unsqueeze(-1), torch.zeros_like(y), y))
 
     @torch.inference_mode()
-    def prefill(self, tokens, req_ids):
+    def prefill(self, tokens, req_ids, chunk_size=None):
         """Ragged prompts -> fp32 logits [n_req, vocab] of each prompt's last token; fills the KV pages
-        (prefill_single_device, model.py:451-465)."""
+        (prefill_single_device, model.py:451-465).  chunk_size = c: the first c tokens of every prompt run here, the rest in
+        rounds of prefill_continue with at most c tokens per request (a request whose prompt is exhausted leaves the later
+        rounds), so no round holds more than n_req * c rows.  An fp8 K / V cache raises NotImplementedError first."""
         from .deepseek_v3 import VarLens
+
+        if chunk_size is not None:
+            c = int(chunk_size)
+            if c < 1:
+                raise ValueError(f"chunk_size={chunk_size}: at least one token per round")
+            if self.args.kv_cache_dtype == "fp8":
+                raise NotImplementedError("chunked prefill attends over bf16 K / V pages; kv_cache_dtype='fp8' is not implemented")
+            req_ids = list(req_ids)
+            logits = self.prefill([list(t[:c]) for t in tokens], req_ids)
+            done = c
+            while True:
+                live = [i for i, t in enumerate(tokens) if len(t) > done]
+                if not live:
+                    return logits
+                out = self.prefill_continue([list(tokens[i][done : done + c]) for i in live], [req_ids[i] for i in live])
+                logits[torch.tensor(live, device=logits.device)] = out  # a later round overwrites it until the prompt ends
+                done += c
 
         from . import graphs
 
@@ -275,9 +313,42 @@ class LlamaDecoder(torch.nn.Module):
         return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight)).float()
 
     @torch.inference_mode()
+    def prefill_continue(self, tokens, req_ids):
+        """Ragged chunks of new tokens for requests that are already cached (a conversation's next turn, the next chunk of a
+        long prompt, a draft model's catch-up) -> fp32 logits [n_req, vocab] of each chunk's last token; appends their K / V
+        rows.  Positions, and so cos / sin, continue from each request's cached length.  The attention reads the pages
+        (LlamaAttention.prefill_forward_paged); everything else is prefill's stack on the new rows.  kv_cache_dtype="fp8"
+        raises NotImplementedError before anything changes."""
+        from .deepseek_v3 import VarLens
+
+        from . import graphs
+
+        if self.args.kv_cache_dtype == "fp8":
+            raise NotImplementedError("continued prefill attends over bf16 K / V pages; kv_cache_dtype='fp8' is not implemented")
+        req_ids = list(req_ids)
+        assert len(tokens) == len(req_ids) and all(len(t) >= 1 for t in tokens)
+        for r, t in zip(req_ids, tokens):
+            assert self.cache.seq_lens[r] + len(t) <= self.cos_table.shape[0], \
+                f"request {r!r}: {self.cache.seq_lens[r]} + {len(t)} tokens exceed max_position_embeddings={self.cos_table.shape[0]}"
+        graphs.sweep_if_memory_was_recycled()
+        varlens = VarLens(tokens, self.device)
+        varlens.continued = True
+        self.cache.prepare_cache_prefill_continue(req_ids, varlens)
+        pos = self.cache.get_continue_position_ids()
+        flat = torch.tensor([t for seq in tokens for t in seq], dtype=torch.int64, device=self.device)
+        cos, sin = self.cos_table[pos], self.sin_table[pos]
+        h, pending = self.embed(flat), None
+        for layer in self.layers:
+            h, pending = layer(h, pending, cos, sin, varlens)
+        last = torch.tensor([p - 1 for p in varlens.cpu_prefix_lens[1:]], dtype=torch.int64, device=self.device)
+        h = ops.rms_norm(h[last], self.norm, self.args.norm_eps, add=tp.resolve(pending)[last].contiguous())[1]
+        self.cache.finalize_cache_all_prefill_continue(req_ids)
+        return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight)).float()
+
+    @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, req_ids=None, use_graph=True, temperatures=None, top_ks=None,
-                 top_ps=None, frequency_penalties=None, generator=None):
-        """Prefill, then max_new_tokens - 1 decode steps; returns [n_req, max_new_tokens] int64 and frees the
+                 top_ps=None, frequency_penalties=None, generator=None, prefill_chunk_size=None):
+        """Prefill (prefill_chunk_size: in chunks, prefill's chunk_size), then max_new_tokens - 1 decode steps; returns [n_req, max_new_tokens] int64 and frees the
         requests' pages.  Token selection is executor.py:82-112 on the device (chitu_amd.sampling): greedy
         unless some top_k > 1 (then per-request temperature / top-k / top-p sampling, uniforms from
         `generator`), with an optional per-request frequency penalty; tokens never visit the host."""
@@ -286,7 +357,8 @@ class LlamaDecoder(torch.nn.Module):
         req_ids = [f"gen{i}" for i in range(len(prompts))] if req_ids is None else list(req_ids)
         pick = DeviceSampler(len(prompts), max_new_tokens, self.device, temperatures, top_ks, top_ps,
                              frequency_penalties, generator)
-        tok = pick(self.prefill(prompts, req_ids))
+        tok = pick(self.prefill(prompts, req_ids) if prefill_chunk_size is None else
+                   self.prefill(prompts, req_ids, chunk_size=prefill_chunk_size))
         out = [tok]
         for _ in range(max_new_tokens - 1):
             self.cache.prepare_cache_decode(req_ids)

@@ -21,7 +21,7 @@
 extern "C" {
 #endif
 
-#define CHITU_HIP_ABI_VERSION 12  /* 12: + chitu_hip_speculative_verify_sampled (verification against a draft that was itself sampled: accept with min(1, p / q), replace from max(p - q, 0), in 128-bit integers), additive only.  11: + chitu_hip_speculative_verify (draft verification of speculative decoding with sampling, next to chitu_hip_sample), additive only.  10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
+#define CHITU_HIP_ABI_VERSION 13  /* 13: + chitu_hip_gqa_prefill_paged (the GQA / MHA flash prefill with its keys read through the block table: continued and chunked prefill over the paged bf16 K / V cache), additive only.  12: + chitu_hip_speculative_verify_sampled (verification against a draft that was itself sampled: accept with min(1, p / q), replace from max(p - q, 0), in 128-bit integers), additive only.  11: + chitu_hip_speculative_verify (draft verification of speculative decoding with sampling, next to chitu_hip_sample), additive only.  10: + chitu_hip_mla_decode_multi, chitu_hip_mla_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the MLA paged decode), additive only.  9: + chitu_hip_gqa_decode_multi, chitu_hip_gqa_decode_multi_kv_fp8 (q_len <= 8 query tokens per sequence on the GQA / MHA paged decode), additive only.  8: + chitu_hip_gqa_decode_window, chitu_hip_gqa_decode_kv_fp8_window, chitu_hip_gqa_prefill_window (sliding window and soft cap of the GQA / MHA decode and prefill), additive only.  7: + the five entries of the fp8 K / V cache of the GQA / MHA decode (chitu_hip_gqa_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_gqa_qkv_post_kv_fp8, chitu_hip_gqa_decode_kv_fp8), additive only; chitu_hip_gqa_decode now also refuses q / cache bases that are not 16-byte aligned (it always loaded 16 bytes).  6: + the four entries of the fp8 latent KV cache (chitu_hip_mla_kv_quant_fp8 / _dequant_fp8 / _append_fp8, chitu_hip_mla_decode_kv_fp8), additive only.  5: + chitu_hip_moe_gemm1_silu_mxfp4_tiled / chitu_hip_moe_gemm2_mxfp4_tiled (prefill form of the MXFP4 experts), additive only.  4: + the five MXFP4 (W4A8) expert entries chitu_hip_*_mxfp4, additive only.  3 (round 6): + chitu_hip_mla_decode_merge_uv_quant_fp8 / _tickets_bytes; INTEGRATION.md lists what 2 -> 3 removed or tightened */
 
 /* ---- fused MoE: token alignment -------------------------------------------------
  * Replaces chitu_backend.cuda_moe_align_block_size (reference csrc/binding.cpp:11,
@@ -573,6 +573,34 @@ int chitu_hip_gqa_prefill_window(const void* q_bf16, int64_t q_stride_t, int64_t
                                  int64_t v_stride_h, const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen,
                                  float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
                                  int32_t window_left, float softcap, void* stream);
+
+/* chitu_hip_gqa_prefill_paged: chitu_hip_gqa_prefill_window with the keys read through a block table -- continued / chunked prefill over
+ * the paged K / V cache.  The seqlen_q != seqlen_k, bottom-right aligned causal case of attn_varlen_func (chitu/attn_backend.py:39-90,
+ * separate cu_seqlens_q / cu_seqlens_k) and of attn_with_kvcache at any seqlen_q (chitu/attn_backend.py:92-164); the reference forwards
+ * both to flash_attn, the arithmetic is RefAttnBackend._attention, :294-392.
+ *   q [T, q_heads, 128] bf16, ragged by cu_seqlens_q [n_seq + 1] i32 (strides and alignment as in chitu_hip_gqa_prefill);
+ *   k_cache / v_cache [num_pages, page_size, kv_heads, 128] bf16, page_size % 16 == 0, block_table rows [table_stride] i32 per
+ *   sequence as in chitu_hip_gqa_decode; seqlens_k[s] = L_s counts ALL keys of sequence s, the n_s = cu_seqlens_q[s + 1] -
+ *   cu_seqlens_q[s] rows of this call included (appended before the call, as for chitu_hip_gqa_decode_multi); max_seqlen_q bounds the
+ *   grid; out [T, q_heads, 128] bf16 contiguous.
+ *   Query i of sequence s sits at position L_s - n_s + i and sees key k iff k <= L_s - n_s + i and, with window_left = W >= 0,
+ *   k >= L_s - n_s + i - W.  A query at a negative position gives zeros.  softcap as in chitu_hip_gqa_prefill_window; (-1, 0.0)
+ *   launch the kernel without the window / cap code.
+ * Memory: rows at positions >= L_s and rows before a block's window are never read, whatever they hold, and neither is a table
+ * entry of a page that holds no key in [lowest visible key, L_s) (tile rows outside repeat key L_s - 1 / the lowest visible key).
+ * Without window and cap: with n_s = L_s the output is bit-identical to chitu_hip_gqa_prefill on the same rows laid out contiguously,
+ * under any block table; with a prefix L_s - n_s that is a multiple of 128 it is bit-identical to rows [L_s - n_s, L_s) of
+ * chitu_hip_gqa_prefill on the whole sequence (64-key tiles start at key 0, query blocks of 128 / G at the first new token).  Other
+ * prefixes: within the attention bar (1e-2 of the peak) -- the wave-wide rescale vote sees other rows.
+ * window_left < -1, softcap < 0 or NaN, strides not multiples of 8, bases not 16-byte aligned, table_stride < 1: CHITU_ERR_BAD_ARG;
+ * head_dim != 128, G not a power of two <= 32, page_size % 16 != 0: CHITU_ERR_UNSUPPORTED; all before any launch.  One launch
+ * (csrc/gqa_prefill_flash.hip, kPaged); the pages are read once per 128 / G query tokens. */
+int chitu_hip_gqa_prefill_paged(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_cache,
+                                const void* v_cache, int64_t num_pages, int32_t page_size, int32_t kv_heads,
+                                const int32_t* block_table, int32_t table_stride, const int32_t* cu_seqlens_q,
+                                const int32_t* seqlens_k, int32_t n_seq, int32_t max_seqlen_q, float softmax_scale,
+                                void* out_bf16, int32_t q_heads, int32_t head_dim, int32_t window_left, float softcap,
+                                void* stream);
 
 /* chitu_hip_mla_decode (num_splits >= 2) AND the merge + W_UV projection + act_quant of the entry below in ONE launch:
  * AttentionDeepSeekV3.decode_forward's mla_attn_with_kvcache -> einsum("bshc,hdc->bshd") -> act_quant of wo's input

@@ -2,7 +2,14 @@
 """Prefill timing of one TP=8 rank shard of DeepSeek-R1 FP8: python tools/prefill_bench.py [layers=8] [T ...]
 One prompt of T tokens through `DeepSeekV3Decoder.prefill` (eager launches: absorb-mode MLA prefill kernel, fp8 GEMMs
 that stream the weights once per 64 rows, fused MoE over T * 8 slots), T in {128, 512, 2048}; ms per layer and the
-rank's tokens/s extrapolated to 61 layers.  Decode is the metric; this records where the step before it stands."""
+rank's tokens/s extrapolated to 61 layers.  Decode is the metric; this records where the step before it stands.
+
+python tools/prefill_bench.py --paged-gqa [--layers 4] [--kernel-only] [--out FILE]: what the block table costs the GQA flash prefill, and what
+continued prefill buys.  (1) Llama-3-8B heads (32 q / 8 kv), prefix 0, n = 2048 and 8192 new tokens, pages of 16 and
+512 tokens in a shuffled pool: chitu_hip_gqa_prefill on the contiguous rows against chitu_hip_gqa_prefill_paged over the pages, in
+ONE process, launches alternated after warm-up, 5 back-to-back launches per timed interval; the outputs are checked bit-identical
+first.  (2) A Llama-3-8B-shaped stack of --layers layers with a 2048-token prefix cached: prefill_continue of 512 tokens against the
+same 512 tokens as 64 decode_multi steps of 8 (graph replay), alternated, the cache rolled back in between.  Median [min .. max]."""
 import json
 import os
 import sys
@@ -43,5 +50,117 @@ def main():
                           "rank_tok_s_at_61_layers": round(T / (best / layers * 61), 1)}), flush=True)
 
 
+def _alternate(arms, warmup, repeats, per):
+    """{name: callable} run in turn -> {name: [us per call]}; `per` back-to-back calls per timed interval"""
+    out = {k: [] for k in arms}
+    for it in range(warmup + repeats):
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(per):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                out[k].append(e0.elapsed_time(e1) * 1e3 / per)
+    return out
+
+
+def _stats(v):
+    import statistics
+
+    return {"median_us": round(statistics.median(v), 1), "min_us": round(min(v), 1), "max_us": round(max(v), 1), "repeats": len(v)}
+
+
+def _box():
+    import subprocess
+
+    try:
+        res = subprocess.run(["rocm-smi", "-d", "0", "--showuniqueid"], capture_output=True, text=True, timeout=10)
+        ids = [ln.split(":")[-1].strip() for ln in res.stdout.splitlines() if ln.strip().startswith("GPU[")]
+        return ids[0] if ids else f"no answer (rc {res.returncode})"
+    except Exception as exc:  # noqa: BLE001
+        return f"unavailable: {type(exc).__name__}"
+
+
+@torch.inference_mode()
+def paged_gqa_main():
+    import argparse
+
+    from chitu_amd.attn_backend import HipAttnBackend
+    from chitu_amd.cache_manager import PagedKVCacheManager
+    from chitu_amd.llama import LlamaArgs, LlamaDecoder, init_synthetic_
+
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--paged-gqa", action="store_true")
+    ap.add_argument("--layers", type=int, default=4)
+    ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--kernel-only", action="store_true", help="part (1) only")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows = [{"box": _box(), "device": torch.cuda.get_device_name(0)}]
+    print(json.dumps(rows[0]), flush=True)
+    Hq, Hkv = 32, 8
+    be = HipAttnBackend(local_n_heads=Hq, max_seq_len=8192)
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for n in (2048, 8192):
+        q = (torch.randn(n, Hq, 128, device="cuda", generator=g) * 0.5).to(torch.bfloat16)
+        k = torch.randn(n, Hkv, 128, device="cuda", generator=g).to(torch.bfloat16)
+        v = torch.randn(n, Hkv, 128, device="cuda", generator=g).to(torch.bfloat16)
+        cu = torch.tensor([0, n], dtype=torch.int32, device="cuda")
+        lens = torch.tensor([n], dtype=torch.int32, device="cuda")
+        for page in (16, 512):
+            pages = n // page
+            perm = torch.randperm(pages + 3, device="cuda", generator=g)[:pages]
+            kc = torch.zeros(pages + 3, page, Hkv, 128, dtype=torch.bfloat16, device="cuda")
+            vc = torch.zeros_like(kc)
+            kc[perm], vc[perm] = k.view(pages, page, Hkv, 128), v.view(pages, page, Hkv, 128)
+            table = perm.to(torch.int32).view(1, pages).contiguous()
+            arms = {"contiguous": lambda: be.attn_varlen_func(q, k, v, cu, cu, n, n, causal=True),
+                    "paged": lambda: be.attn_varlen_with_kvcache(q, kc, vc, cu, lens, table, n)}
+            if not torch.equal(arms["contiguous"](), arms["paged"]()):
+                rows.append({"n": n, "page": page, "error": "outputs differ: no times"})
+                print(json.dumps(rows[-1]), flush=True)
+                continue
+            t = {k_: _stats(v_) for k_, v_ in _alternate(arms, a.warmup, a.repeats, 5).items()}
+            rows.append({"what": "kernel", "Hq": Hq, "Hkv": Hkv, "prefix": 0, "n": n, "page": page, **t,
+                         "paged_over_contiguous": round(t["paged"]["median_us"] / t["contiguous"]["median_us"], 4)})
+            print(json.dumps(rows[-1]), flush=True)
+            del kc, vc
+    if a.kernel_only:
+        return
+    # (2) the model path: 512 tokens onto a cached 2048-token prefix
+    args = LlamaArgs(n_layers=a.layers)
+    cache = PagedKVCacheManager(0, a.layers, num_hot_req=1, block_size=256, max_seq_len=4096, device="cuda",
+                                n_local_kv_heads=args.n_kv_heads, head_dim=128, dtype=torch.bfloat16)
+    model = LlamaDecoder(args, cache, HipAttnBackend(local_n_heads=args.n_heads, max_seq_len=4096), max_position_embeddings=4096, device="cuda")
+    init_synthetic_(model, seed=1)
+    gc = torch.Generator().manual_seed(0)
+    prompt = torch.randint(100, 1000, (2048,), generator=gc).tolist()
+    tail = torch.randint(100, 1000, (512,), generator=gc)
+    model.prefill([prompt], ["r"])
+    steps = tail.view(64, 1, 8).cuda()
+
+    def continued():
+        model.prefill_continue([tail.tolist()], ["r"])
+        cache.rollback(["r"], [512])
+
+    def multi_steps():
+        for i in range(64):
+            cache.prepare_block_table_for_decode_multi(["r"], 8)
+            model.decode_multi(steps[i], use_graph=True)
+            cache.finalize_cache_multi_decode(["r"], [8])
+        cache.rollback(["r"], [512])
+
+    t = {k_: _stats(v_) for k_, v_ in _alternate({"prefill_continue_512": continued, "decode_multi_64x8": multi_steps}, 2, 7, 1).items()}
+    rows.append({"what": "model", "layers": a.layers, "prefix": 2048, "new_tokens": 512, **t,
+                 "continue_over_multi": round(t["prefill_continue_512"]["median_us"] / t["decode_multi_64x8"]["median_us"], 4)})
+    print(json.dumps(rows[-1]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    paged_gqa_main() if "--paged-gqa" in sys.argv else main()
