@@ -424,6 +424,16 @@ static int gemm_wk(int tiles, int KB) {
     return WK;
 }
 
+// Do the bf16 rows [M][cols] at a (row stride a_stride) and at b (b_stride) share a byte?  sum_out is written by workgroup 0
+// while every other workgroup of the grid still reads x and add for its own copy of the prologue: a sum_out inside either
+// would hand the later workgroups the NEW residual stream as their input.  (chitu_hip_rmsnorm can run in place: there one
+// workgroup owns a row.)
+static bool rows_overlap(const void* a, int64_t a_stride, int64_t a_cols, const void* b, int64_t b_stride, int64_t b_cols, int64_t M) {
+    const char *a0 = (const char*)a, *b0 = (const char*)b;
+    const char *a1 = a0 + ((M - 1) * a_stride + a_cols) * 2, *b1 = b0 + ((M - 1) * b_stride + b_cols) * 2;
+    return a0 < b1 && b0 < a1;
+}
+
 static bool fused_norm_shape_ok(int64_t M, int64_t K) {
     return M >= 1 && M <= kFusedNormMaxRows && K % 64 == 0 && K >= 512 && K <= kNormWideThreads * 8 && M * K * 2 <= 48 * 1024;
 }
@@ -447,6 +457,9 @@ extern "C" int chitu_hip_bf16_gemm_add_norm(const void* x_bf16, int64_t x_row_st
     const int WK = gemm_wk(tiles, KB);
     if (WK < 4) return CHITU_ERR_UNSUPPORTED;
     const int per_wave = KB / WK;
+    // (after the shape limits: an unfit shape is CHITU_ERR_UNSUPPORTED whatever its pointers)
+    CHITU_REQUIRE(!rows_overlap(sum_out_bf16, sum_row_stride, K, x_bf16, x_row_stride, K, M) &&
+                  !rows_overlap(sum_out_bf16, sum_row_stride, K, add_bf16, add_row_stride, K + term2_off, M));
     const size_t lds = (size_t)M * K * 2;
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCH_MR(WKV, DV, MRV)                                                                                          \
@@ -498,6 +511,9 @@ extern "C" int chitu_hip_bf16_gemm_add_norm_qkv_post(
     const int WK = gemm_wk(tiles, KB);
     if (WK < 4) return CHITU_ERR_UNSUPPORTED;
     const int per_wave = KB / WK;
+    // (after the shape limits: an unfit shape is CHITU_ERR_UNSUPPORTED whatever its pointers)
+    CHITU_REQUIRE(!rows_overlap(sum_out_bf16, sum_row_stride, K, x_bf16, x_row_stride, K, M) &&
+                  !rows_overlap(sum_out_bf16, sum_row_stride, K, add_bf16, add_row_stride, K, M));
     const size_t lds = (size_t)M * K * 2;
     hipStream_t st = (hipStream_t)stream;
     const QkvPostArgs qa{cos, sin, (bf16_t*)k_cache, (bf16_t*)v_cache, num_pages, page_table, old_seq_lens,
@@ -545,6 +561,9 @@ extern "C" int chitu_hip_bf16_gemm_silu_add_norm(const void* x_bf16, int64_t x_r
     const int KB = (int)(K / 64), tiles = (int)((inter + 15) / 16);
     const int WK = gemm_wk(tiles, KB);
     if (WK < 4) return CHITU_ERR_UNSUPPORTED;
+    // (after the shape limits: an unfit shape is CHITU_ERR_UNSUPPORTED whatever its pointers)
+    CHITU_REQUIRE(!rows_overlap(sum_out_bf16, sum_row_stride, K, x_bf16, x_row_stride, K, M) &&
+                  !rows_overlap(sum_out_bf16, sum_row_stride, K, add_bf16, add_row_stride, K, M));
     const size_t lds = (size_t)M * K * 2;
     hipStream_t st = (hipStream_t)stream;
 #define LAUNCHS_MR(WKV, MRV)                                                                                             \

@@ -317,7 +317,7 @@ int chitu_hip_bf16_gemm_silu(const void* x_bf16, const void* w13_bf16, void* out
  * TransformerBlockDeepSeekV3.forward (model_deepseek_v3.py:1107-1113): x = x + ffn(...); attn(attn_norm(x)) with the first
  * linear of the attention (wqkv_a; linear_deepseek_v3 :98-100 = act_quant_deepseek_v3 + fp8_gemm_deepseek_v3) in ONE launch:
  *   a[m]       = add_terms == 1 ? add[m] : bf16(sum_k float(add[m, k, :]))   (the experts' top-k sum, fused_moe.py:1299-1305)
- *   sum_out[m] = bf16(x[m] + a[m])                                          (the new residual stream)
+ *   sum_out[m] = bf16(x[m] + a[m])                                          (the new residual stream; must not overlap x or add)
  *   y[m]       = bf16((sum_out[m] * rsqrt(mean(sum_out[m]^2) + eps)) * norm_weight);  (q, s) = act_quant(y, 128)
  *   out        = fp8_gemm(q, s, w_fp8, w_scale)                              [M, N], out_dtype as chitu_hip_fp8_gemm_blockscale
  * Bit-identical to chitu_hip_rmsnorm(add, add_terms, quant_mode = 1) followed by chitu_hip_fp8_gemm_blockscale (same
@@ -333,7 +333,10 @@ int chitu_hip_fp8_gemm_add_norm(const void* x_bf16, int64_t x_row_stride, const 
  * TransformerBlock (models/model.py:246-251): h = x + attention(attention_norm(x)); out = h + ffn(ffn_norm(h)) --
  * the add and the norm (RMSNorm.forward, models/model.py:29-78) in front of a layer's qkv projection and of its
  * gate/up projection, folded into those launches:
- *   sum_out[m] = bf16(x[m] + add[m])                       (the new residual stream; may alias x or add)
+ *   sum_out[m] = bf16(x[m] + add[m])                       (the new residual stream; must NOT overlap x or add, taken
+ *                                                           from their first to their last row, gaps included: every
+ *                                                           workgroup of the GEMM re-reads both while workgroup 0 writes
+ *                                                           sum_out -- an overlapping sum_out is CHITU_ERR_BAD_ARG)
  *   y[m]       = bf16((sum_out[m] * rsqrt(mean(sum_out[m]^2) + eps)) * norm_weight)
  *   out        = y . w^T                                   (chitu_hip_bf16_gemm_add_norm)
  *   out        = silu(y . w1^T) * (y . w3^T)               (chitu_hip_bf16_gemm_silu_add_norm, w13 = [w1; w3])
