@@ -447,16 +447,19 @@ def _merge_group(state: Mapping[str, torch.Tensor], parts, merged: str) -> Dict[
 
 
 def preprocess_hf_llama(state: Mapping[str, torch.Tensor], n_heads: int, n_kv_heads: Optional[int], dim: int, rank: int = 0,
-                        world: int = 1, mixtral: bool = False, router_row_parallel: bool = True) -> Dict[str, torch.Tensor]:
+                        world: int = 1, mixtral: bool = False, router_row_parallel: bool = True,
+                        head_dim: Optional[int] = None) -> Dict[str, torch.Tensor]:
     """HF names -> this TP rank's tensors under the reference's final names (qkv_proj / gate_up_proj merged per rank).
     router_row_parallel: the reference shards Mixtral's router along its INPUT dimension and all-reduces the logits
-    (model_hf_mixtral.py:157-160); chitu_amd.mixtral keeps the [experts, dim] matrix whole on every rank (False)."""
+    (model_hf_mixtral.py:157-160); chitu_amd.mixtral keeps the [experts, dim] matrix whole on every rank (False).
+    head_dim: the width of one head where a file ships qkv merged and TP > 1 has to split it; None: dim // n_heads (Qwen3
+    decouples the two).  Per-head norm weights (Qwen3's q_norm / k_norm) match no parallel layer and stay whole."""
     n_kv = n_heads if n_kv_heads is None else n_kv_heads
     st = strip_model_prefix(state)
     if mixtral:
         st = map_mixtral_names(st)
     if world > 1:
-        st = split_merged_gate_up(split_merged_qkv(st, n_heads, n_kv, dim // n_heads))
+        st = split_merged_gate_up(split_merged_qkv(st, n_heads, n_kv, dim // n_heads if head_dim is None else head_dim))
         row = HF_LLAMA_ROW + (("gate",) if mixtral and router_row_parallel else ())
         st = chunk_for_tensor_parallel(st, rank, world, column=HF_LLAMA_COLUMN, row=row)
     st = _merge_group(st, ("q_proj", "k_proj", "v_proj"), "qkv_proj")
@@ -466,6 +469,7 @@ def preprocess_hf_llama(state: Mapping[str, torch.Tensor], n_heads: int, n_kv_he
 _LLAMA_MODULE_NAMES = (("embed_tokens.weight", "embed_weight"), ("lm_head.weight", "head_weight"), ("norm.weight", "norm"),
                        (".input_layernorm.weight", ".attn_norm"), (".post_attention_layernorm.weight", ".ffn_norm"),
                        (".self_attn.qkv_proj.weight", ".attn.wqkv"), (".self_attn.o_proj.weight", ".attn.wo"),
+                       (".self_attn.q_norm.weight", ".attn.q_norm"), (".self_attn.k_norm.weight", ".attn.k_norm"),
                        (".mlp.gate_up_proj.weight", ".ffn.w13"), (".mlp.down_proj.weight", ".ffn.w2"), (".mlp.gate.weight", ".ffn.gate"))
 
 
@@ -530,8 +534,11 @@ def load_checkpoint_hf_llama(model, path: str, rank: int = 0, world: int = 1, sk
         load_deepseek_v3(model, state)
         return
     mixtral = hasattr(args, "num_local_experts")
+    if getattr(args, "tie_word_embeddings", False) and "lm_head.weight" not in state:
+        # the small Qwen3 sizes ship no output head: it is the embedding (sharded by vocabulary rows like it below)
+        state["lm_head.weight"] = state["model.embed_tokens.weight" if "model.embed_tokens.weight" in state else "embed_tokens.weight"]
     st = preprocess_hf_llama(state, args.n_heads, args.n_kv_heads, args.dim, rank, world, mixtral=mixtral,
-                             router_row_parallel=False)
+                             router_row_parallel=False, head_dim=args.head_dim)
     st = to_mixtral_module_names(st, args.num_local_experts) if mixtral else to_llama_module_names(st)
     load_deepseek_v3(model, st)  # the generic strict, shape- and dtype-checked in-place copy
 

@@ -94,6 +94,14 @@ class LlamaAttention(torch.nn.Module):
         # merged [wq | wk | wv] rows (ColumnParallel: heads split across ranks), wo RowParallel
         self.wqkv = _param((self.hq + 2 * self.hkv) * self.hd, args.dim, device=device)
         self.wo = _param(args.dim, self.hq * self.hd, device=device)
+        # Qwen3: an RMSNorm with a learned [head_dim] weight on every q head and every k head, after the projection and before
+        # RoPE (replicated under TP: the weights are per channel, not per head)
+        self.qk_norm = bool(getattr(args, "qk_norm", False))
+        if self.qk_norm:
+            assert self.hd == 128, "the head-norm launches are head_dim 128"
+            self.q_norm = _param(self.hd, device=device)
+            self.k_norm = _param(self.hd, device=device)
+            self.qk_eps = args.norm_eps
 
     def decode_forward_paged(self, x, cos, sin, q_len=1):
         """x = attn_norm(h) bf16 [bs, dim] -> wo(attention) before the all-reduce (model.py:167-198)."""
@@ -112,6 +120,11 @@ class LlamaAttention(torch.nn.Module):
         qkv = qkv.view(bs, self.hq + 2 * self.hkv, self.hd)
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
         # RoPE(q, k) + append of k and v to their pages: one launch (fp8 cache: with quantising stores)
+        if self.qk_norm:  # the head norm in front of the rotation, same launch
+            post = ops.gqa_qkv_norm_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_norm_post
+            q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), self.q_norm, self.k_norm,
+                     self.qk_eps, rotary_type=self.rotary_type)
+            return self.decode_from_q(q, q_len)
         post = ops.gqa_qkv_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_post
         q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), rotary_type=self.rotary_type)
         return self.decode_from_q(q, q_len)
@@ -137,14 +150,22 @@ class LlamaAttention(torch.nn.Module):
     def decode_from_residual(self, x, pending, norm_weight, eps, cos, sin, q_len=1):
         """Small decode batches: residual add + attn_norm + wqkv projection [+ RoPE and the K / V page append when the
         rotary pairs are interleaved] in ONE launch.  Returns (x + pending, wo(attention) before the all-reduce).  The fused
-        epilogue writes bf16 page rows: an fp8 cache takes the two-launch form of "hf-llama"."""
-        if self.rotary_type == "llama" and not self.fp8_kv:
+        epilogue writes bf16 page rows: an fp8 cache takes the two-launch form of "hf-llama", and so does a model with a head norm
+        (the epilogue does not normalise)."""
+        if self.rotary_type == "llama" and not self.fp8_kv and not self.qk_norm:
             k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
             x, qkv = ops.bf16_linear_add_norm_qkv_post(
                 x, pending, norm_weight, eps, self.wqkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len))
             return x, self.decode_from_q(qkv[:, : self.hq], q_len)
         x, qkv = ops.bf16_linear_add_norm(x, pending, norm_weight, eps, self.wqkv)
         return x, self.decode_from_qkv(qkv, cos, sin, q_len)
+
+    def _rotate(self, qkv, cos, sin):
+        """Prefill: RoPE (behind the head norm, when the model has one) on the q and k heads of qkv [T, hq + 2 hkv, hd]."""
+        q, k = qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv]
+        if self.qk_norm:
+            return ops.qk_norm_rope(q, k, self.q_norm, self.k_norm, self.qk_eps, cos, sin, rotary_type=self.rotary_type)
+        return ops.apply_rotary_pos_emb(q, k, cos, sin, rotary_type=self.rotary_type)
 
     def prefill_forward(self, x, cos, sin, varlens):
         """models/model.py:104-132: projections on all T prompt tokens, RoPE, page writes by the cache
@@ -154,7 +175,7 @@ class LlamaAttention(torch.nn.Module):
             return self.prefill_forward_paged(x, cos, sin, varlens)
         T = x.shape[0]
         qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
-        q, k = ops.apply_rotary_pos_emb(qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv], cos, sin, rotary_type=self.rotary_type)
+        q, k = self._rotate(qkv, cos, sin)
         v = qkv[:, self.hq + self.hkv :].contiguous()
         if self.fp8_kv:
             # the pages take the quantised rows (the same index_copy_ scatter, over byte rows); attention runs over the
@@ -174,7 +195,7 @@ class LlamaAttention(torch.nn.Module):
         assert not self.fp8_kv, "continued prefill reads bf16 K / V pages"
         T = x.shape[0]
         qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
-        q, k = ops.apply_rotary_pos_emb(qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv], cos, sin, rotary_type=self.rotary_type)
+        q, k = self._rotate(qkv, cos, sin)
         v = qkv[:, self.hq + self.hkv :].contiguous()
         self.cache.finalize_cache_bylayer_prefill_continue(k, v, self.layer_id)
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
@@ -199,9 +220,11 @@ class LlamaFeedForward(torch.nn.Module):
 
 
 class LlamaBlock(torch.nn.Module):
+    rotary_type = "llama"  # subclasses (Qwen3) name the half-split layout
+
     def __init__(self, layer_id, args, cache, attn_backend, device=None):
         super().__init__()
-        self.attn = LlamaAttention(args, layer_id, cache, attn_backend, device)
+        self.attn = LlamaAttention(args, layer_id, cache, attn_backend, device, rotary_type=self.rotary_type)
         self.ffn = LlamaFeedForward(args, device)
         self.attn_norm = _param(args.dim, device=device)
         self.ffn_norm = _param(args.dim, device=device)

@@ -560,6 +560,88 @@ def gqa_qkv_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page
     return qkv[:, :q_heads]
 
 
+def _check_head_norm_weights(q_norm_weight, k_norm_weight):
+    for w in (q_norm_weight, k_norm_weight):
+        assert w.dtype == torch.bfloat16 and tuple(w.shape) == (128,) and w.is_contiguous()
+
+
+def _gqa_qkv_norm_post(entry, what, qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight,
+                       k_norm_weight, eps, rotary_type):
+    require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight, k_norm_weight)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
+    assert qkv.stride(2) == 1 and qkv.stride(1) == 128 and qkv.stride(0) % 8 == 0, "dense heads; only the row stride is free"
+    _check_head_norm_weights(q_norm_weight, k_norm_weight)
+    assert k_cache.shape[2] == kv_heads and page_table.dtype == torch.int32 and page_table.stride(1) == 1
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and old_seq_lens.dtype == torch.int32
+    bs = qkv.shape[0]
+    assert cos.shape == (bs, 64) and sin.shape == (bs, 64) and page_table.shape[0] >= bs and page_table.is_contiguous()
+    assert old_seq_lens.shape[0] >= bs and old_seq_lens.is_contiguous()
+    check(
+        getattr(_lib.lib(), entry)(
+            ptr(qkv), i64(qkv.stride(0)), i32(q_heads), i32(kv_heads), i32(128), ptr(cos), ptr(sin),
+            i32(0 if rotary_type == "llama" else 1), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
+            ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), ptr(q_norm_weight), ptr(k_norm_weight),
+            f32(eps), stream_ptr(),
+        ),
+        what,
+    )
+    return qkv[:, :q_heads]
+
+
+def gqa_qkv_norm_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight, k_norm_weight,
+                      eps, rotary_type="llama"):
+    """gqa_qkv_post with Qwen3's per-head RMSNorm in front of the rotation, one launch: every q head and every k head is
+    normalised (weights [128] bf16, fp32 arithmetic, one bf16 rounding) and then rotated; q in place, k into the token's page
+    row, v copied.  qkv [bs, q_heads + 2*kv_heads, 128] bf16 (the row stride may be padded); returns the q view."""
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
+    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape and k_cache.dtype == torch.bfloat16
+    assert v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4 and k_cache.shape[3] == 128
+    return _gqa_qkv_norm_post("chitu_ext_gqa_qkv_norm_post", "gqa_qkv_norm_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
+                              page_table, old_seq_lens, q_norm_weight, k_norm_weight, eps, rotary_type)
+
+
+def gqa_qkv_norm_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight,
+                             k_norm_weight, eps, rotary_type="llama"):
+    """gqa_qkv_norm_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): the bytes of gqa_kv_quant_fp8 on the
+    rows gqa_qkv_norm_post writes.  One launch; returns the q view."""
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
+    _check_gqa_fp8_caches(k_cache, v_cache)
+    return _gqa_qkv_norm_post("chitu_ext_gqa_qkv_norm_post_kv_fp8", "gqa_qkv_norm_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin,
+                              k_cache, v_cache, page_table, old_seq_lens, q_norm_weight, k_norm_weight, eps, rotary_type)
+
+
+def qk_norm_rope(q, k, q_norm_weight, k_norm_weight, eps, cos, sin, rotary_type="hf-llama"):
+    """The prefill form of gqa_qkv_norm_post, no cache: per-head RMSNorm, then RoPE, on q [T, q_heads, 128] and k [T, kv_heads,
+    128] bf16 (strided views of a merged projection allowed: channels dense, strides multiples of 8 elements), the whole
+    prompt in one launch.  cos / sin fp32 [T, 64].  Returns (out_q, out_k), bit-identical to what the decode form produces
+    for the same rows."""
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
+    require_cuda(q, k, cos, sin, q_norm_weight, k_norm_weight)
+    assert q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and q.dim() == 3 and k.dim() == 3
+    assert q.shape[2] == 128 and k.shape[2] == 128 and q.shape[0] == k.shape[0] and q.stride(2) == 1 and k.stride(2) == 1
+    _check_head_norm_weights(q_norm_weight, k_norm_weight)
+    T = q.shape[0]
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+    assert cos.shape == (T, 64) and sin.shape == (T, 64)
+    out_q = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    out_k = torch.empty(k.shape, dtype=k.dtype, device=k.device)
+    if T == 0:
+        return out_q, out_k
+    check(
+        _lib.lib().chitu_ext_qk_norm_rope(
+            ptr(q), ptr(k), ptr(out_q), ptr(out_k), ptr(cos), ptr(sin), ptr(q_norm_weight), ptr(k_norm_weight), f32(eps),
+            i64(T), i32(q.shape[1]), i32(k.shape[1]), i32(128), i64(q.stride(0)), i64(q.stride(1)), i64(k.stride(0)),
+            i64(k.stride(1)), i64(out_q.stride(0)), i64(out_q.stride(1)), i64(out_k.stride(0)), i64(out_k.stride(1)),
+            i32(0 if rotary_type == "llama" else 1), stream_ptr(),
+        ),
+        "qk_norm_rope",
+    )
+    return out_q, out_k
+
+
 def bf16_linear_silu(x: torch.Tensor, w13: torch.Tensor) -> torch.Tensor:
     """silu(x w1^T) * (x w3^T) for w13 = [w1; w3] (bf16), one launch: == silu_and_mul(bf16_linear(x, w13))."""
     require_cuda(x, w13)
