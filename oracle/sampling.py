@@ -15,7 +15,9 @@ prefix rule (position < top_k and exclusive cumsum <= top_p * Z) evaluated on we
 2^40 and truncated, ties in the descending order broken by lower index, the draw an inverse CDF in
 index order for a given uniform u.  In `probs_mode` every operation of the kernel is an IEEE
 operation, so the kernel must match it bit for bit; in logits mode the kernel's exp differs from
-numpy's by an ulp and the tests allow the boundary to move by elements of negligible mass.
+numpy's by an ulp and the tests allow the boundary to move by elements of negligible mass
+(tests/test_gpu_sampler.py), or admit only rows whose every decision keeps a margin of 2^-12 and demand equality
+(tests/sample_exact.py, tests/test_gpu_sample_exact.py).
 """
 
 import numpy as np
