@@ -36,25 +36,7 @@ struct MoeStage {
     float xs, ws;
 };
 
-// write one lane's 4 results (tile columns 2g,2g+1,8+2g,8+2g+1 of token slot) as bf16, scaled by rw
-__device__ __forceinline__ void moe_store_tile(bf16_t* out_row, int n0, int g, int N, const f32x4& acc, float rw) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int n = n0 + h * 8 + 2 * g;
-        const uint16_t a = f32_to_bf16(acc[2 * h] * rw), b = f32_to_bf16(acc[2 * h + 1] * rw);
-        if (n + 1 < N && (N & 1) == 0) *reinterpret_cast<uint32_t*>(out_row + n) = (uint32_t)a | ((uint32_t)b << 16);
-        else {
-            if (n < N) out_row[n] = a;
-            if (n + 1 < N) out_row[n + 1] = b;
-        }
-    }
-}
-
-__device__ __forceinline__ float moe_routed_weight(const void* topk_w, int w_dt, int slot) {
-    if (w_dt == 0) return bf16_to_f32(((const bf16_t*)topk_w)[slot]);
-    if (w_dt == 1) return f16_to_f32(((const uint16_t*)topk_w)[slot]);
-    return ((const float*)topk_w)[slot];
-}
+// (the epilogue pieces moe_store_tile and moe_routed_weight: gemm_common.h, shared with moe_mxfp4.hip)
 
 // ---------------------------------------------------------------- GEMM1: x[token] . W1[e]^T
 // grid (n_tiles / NW, max_mblocks); block 64*WK*NW: NW waves own neighbouring 16-row tiles of the same

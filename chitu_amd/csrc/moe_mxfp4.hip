@@ -24,25 +24,6 @@
 
 namespace chitu {
 
-__device__ __forceinline__ void mx_store_tile(bf16_t* out_row, int n0, int g, int N, const f32x4& acc, float rw) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int n = n0 + h * 8 + 2 * g;
-        const uint16_t a = f32_to_bf16(acc[2 * h] * rw), b = f32_to_bf16(acc[2 * h + 1] * rw);
-        if (n + 1 < N && (N & 1) == 0) *reinterpret_cast<uint32_t*>(out_row + n) = (uint32_t)a | ((uint32_t)b << 16);
-        else {
-            if (n < N) out_row[n] = a;
-            if (n + 1 < N) out_row[n + 1] = b;
-        }
-    }
-}
-
-__device__ __forceinline__ float mx_routed_weight(const void* topk_w, int w_dt, int slot) {
-    if (w_dt == 0) return bf16_to_f32(((const bf16_t*)topk_w)[slot]);
-    if (w_dt == 1) return f16_to_f32(((const uint16_t*)topk_w)[slot]);
-    return ((const float*)topk_w)[slot];
-}
-
 // One step (K blocks 2p, 2p + 1) of NT 16-row tiles sharing one activation row per lane.
 template <int NT>
 struct MxStage {
@@ -171,8 +152,8 @@ __global__ __launch_bounds__(64 * WK) void moe_mx_gemm_kernel(
     }
     if (!mx_reduce<WK, 1>(acc, red, wave, lane)) return;
     if (!valid) return;
-    const float rw = mul_weight ? mx_routed_weight(topk_w, w_dt, slot) : 1.0f;
-    mx_store_tile(out + (size_t)slot * N, n0, g, N, acc[0], rw);
+    const float rw = mul_weight ? moe_routed_weight(topk_w, w_dt, slot) : 1.0f;
+    moe_store_tile(out + (size_t)slot * N, n0, g, N, acc[0], rw);
 }
 
 // ---------------------------------------------------------------- GEMM1 + SiLU-and-mul
@@ -214,7 +195,7 @@ __global__ __launch_bounds__(64 * WK) void moe_mx_gemm1_silu_kernel(
         const float sl = round_bf16(gv / (1.0f + expf(-gv)));
         h[r] = round_bf16(sl * uv);
     }
-    mx_store_tile(out + (size_t)slot * I, n0, g, I, h, 1.0f);
+    moe_store_tile(out + (size_t)slot * I, n0, g, I, h, 1.0f);
 }
 
 // ---------------------------------------------------------------- GEMM2 with the fp8 re-quantisation of h in its prologue
@@ -248,7 +229,7 @@ __global__ __launch_bounds__(256) void moe_mx_gemm2_q_kernel(
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int n0 = (tile_of(r) + t) * 16;
-                if (n0 < N && valid) mx_store_tile(out + (size_t)slot * N, n0, g, N, f32x4{0.f, 0.f, 0.f, 0.f}, 1.0f);
+                if (n0 < N && valid) moe_store_tile(out + (size_t)slot * N, n0, g, N, f32x4{0.f, 0.f, 0.f, 0.f}, 1.0f);
             }
         return;
     }
@@ -287,7 +268,7 @@ __global__ __launch_bounds__(256) void moe_mx_gemm2_q_kernel(
         }
     };
     load_round(wf[0], 0);
-    const float rw = (mul_weight && valid) ? mx_routed_weight(topk_w, w_dt, slot) : 1.0f;
+    const float rw = (mul_weight && valid) ? moe_routed_weight(topk_w, w_dt, slot) : 1.0f;
     float hv[HPW][16];
 #pragma unroll
     for (int q = 0; q < HPW; ++q) {
@@ -351,7 +332,7 @@ __global__ __launch_bounds__(256) void moe_mx_gemm2_q_kernel(
                         acc[2 * h + 1] = __builtin_fmaf(ov[3], xs[ko], acc[2 * h + 1]);
                     }
                 }
-            if (valid && n0 < N) mx_store_tile(out + (size_t)slot * N, n0, g, N, acc, rw);
+            if (valid && n0 < N) moe_store_tile(out + (size_t)slot * N, n0, g, N, acc, rw);
         }
     }
 }

@@ -13,14 +13,15 @@ and reuse a warm workspace.  Here:
      the bit identities between the forms, token permutation, the top-k sum, and the CPU oracles per slot -- whole tensor at
      the family's existing bar and ROW BY ROW (a slot computed from the wrong token or expert is wrong by its whole size).
 
-Mutations tried by hand on the MI355X (other builds of the library, never committed) and what caught them here:
-  - csrc/moe_tiled.hip, store_tile without `if (s >= numel) continue`: the guard rows of sections 2 and 3, all 14 cases of
+Mutations tried by hand on the MI355X (other builds of the library, never committed) and what caught them here (the three
+of the tiled kernels were made in csrc/moe_tiled.hip, before its tile walk and epilogue moved to csrc/moe_tiled_common.h):
+  - csrc/moe_tiled_common.h, store_tile without `if (s >= numel) continue`: the guard rows of sections 2 and 3, all 14 cases of
     chitu_hip_moe_gemm2_fp8_tiled and chitu_hip_moe_gemm1_silu_fp8_tiled ("stored into the guard rows after the output").
     (Run against those two tests only: anywhere else the stray row lies outside the buffer.)
-  - csrc/moe_tiled.hip, `mt_valid = mt` for `mt + 1`: the exact tests of both tiled entries at block_m 128 (zeros in the last
+  - csrc/moe_tiled_common.h, `mt_valid = mt` for `mt + 1`: the exact tests of both tiled entries at block_m 128 (zeros in the last
     live 16-slot sub-tile) and the per-row bar of test_tiled_forms...[fp8-*] on all six patterns (worst row 0.76 .. 1.0).
     tests/test_gpu_moe.py sees this one too (test_prefill_tiled_expert_path_*).
-  - csrc/moe_tiled.hip, `C = nb >> 3` for `(nb + 7) >> 3`: the exact SiLU test of chitu_hip_moe_gemm1_silu_fp8_tiled (4 and 7
+  - csrc/moe_tiled_common.h, `C = nb >> 3` for `(nb + 7) >> 3`: the exact SiLU test of chitu_hip_moe_gemm1_silu_fp8_tiled (4 and 7
     blocks: nothing is computed) and test_tiled_forms...[fp8-*] on all six patterns ("poisoned != unpoisoned" or the per-row
     bar: every pattern has a block count that is no multiple of 8 at one of the two heights); of tests/test_gpu_moe.py only
     the 2048-token case notices (its other cases read the previous call's h).
@@ -270,7 +271,7 @@ def _abi_case(spec, K, w_rows, seed, lo_a, hi_a, lo_w, hi_w):
     return ids, A, W, wts, exact
 
 
-@pytest.mark.parametrize("K,N", [(128, 128), (128, 200), (384, 128), (384, 200)])
+@pytest.mark.parametrize("K,N", [(128, 128), (128, 200), (384, 128), (384, 200), (256, 1160)])
 @pytest.mark.parametrize("name", sorted(PLAIN_ENTRIES))
 def test_plain_grouped_gemm_entries_are_exact_on_integer_data_and_keep_their_guard_rows(name, K, N):
     """Activations and weights are integers in -4..4 (e4m3, exact e2m1 codes, bf16 or int8), every scale a power of two 2^-2..2^2
@@ -279,8 +280,10 @@ def test_plain_grouped_gemm_entries_are_exact_on_integer_data_and_keep_their_gua
     and the output is that value times the routed weight, rounded once to bf16 (the int8 entry rounds the scaled sum to bf16
     first and the product again: with a power-of-two weight the second rounding changes nothing, and the reference below does
     both).  torch.equal for every real slot row; N = 200 is no multiple of 128 nor of 16 (clamped tail rows of the weight
-    tile); the G rows before and after the output keep their sentinel bits (a store to row numel, the id of a padding slot,
-    would land in the first guard row after it).  Run once more with the hottest expert on another rank (expert_map -1):
+    tile); (K, N) = (256, 1160) is ten 128-row tiles of two K blocks each, which the tiled GEMM2 entries walk four to a
+    workgroup (4, 4 and 2 tiles: the last group is partial, its last tile has 8 live rows); the G rows before and after
+    the output keep their sentinel bits (a store to row numel, the id of a padding slot, would land in the first guard row
+    after it).  Run once more with the hottest expert on another rank (expert_map -1):
     its slots, several blocks of them, come out as zeros and nothing else moves."""
     spec = PLAIN_ENTRIES[name]
     routed = spec[5]
