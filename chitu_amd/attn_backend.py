@@ -535,6 +535,50 @@ class HipAttnBackend(AttnBackend):
                                                 softmax_scale=softmax_scale).view(t1 - t0, Hq, D)
         return out
 
+    # ------------------------------------------------------------------ MLA continued prefill over the paged latent cache
+    def mla_attn_varlen_with_kvcache(self, q, kv_cache, cu_seqlens_q, cache_seqlens, block_table, max_seqlen_q, total_keys,
+                                     softmax_scale, gathered=None):
+        """The MLA form of attn_varlen_with_kvcache (no reference counterpart): continued and chunked prefill in absorb mode.
+
+        q [T, H, 576] bf16, sequence s owning rows cu_seqlens_q[s] .. cu_seqlens_q[s + 1]; kv_cache one layer of the latent
+        cache, bf16 [pages, page, 576] or fp8 uint8 [pages, page, 656], with those rows' latent rows already written;
+        cache_seqlens [n_seq] int32 counts ALL keys of a sequence, the new rows included; block_table [n_seq, max_pages] int32;
+        max_seqlen_q bounds the launch; total_keys = sum(cache_seqlens), known to the host (no sync).  Query i of sequence s
+        sits at position cache_seqlens[s] - n_s + i and sees the keys up to itself.  Returns [T, H, 512].
+
+        Two launches: ops.mla_kv_gather copies (bf16) or widens (fp8) every sequence's rows out of the pages into `gathered`
+        (bf16 [>= total_keys, 576]; allocated when None -- a model passes one buffer for all its layers), then
+        chitu_ext2_mla_prefill_flash_continue runs the flash prefill kernel with separate query and key extents over it.
+        With an fp8 cache the queries therefore attend over the QUANTISED rows, their own chunk's included."""
+        from . import ops
+
+        require_cuda(q, kv_cache, cu_seqlens_q, cache_seqlens, block_table)
+        C, R = self.kv_lora_rank, self.qk_rope_head_dim
+        assert (C, R) == (512, 64), "the flash prefill kernel is built for 512 + 64 rows"
+        assert q.dim() == 3 and q.dtype == torch.bfloat16 and q.shape[-1] == C + R
+        assert cache_seqlens.dtype == torch.int32 and cache_seqlens.dim() == 1
+        T, H, _ = q.shape
+        n_seq = cache_seqlens.numel()
+        assert cu_seqlens_q.numel() == n_seq + 1 and block_table.shape[0] == n_seq
+        if T == 0:
+            return q.new_empty(0, H, C)
+        dev = q.device
+        cu_k = torch.zeros(n_seq + 1, dtype=torch.int32, device=dev)
+        torch.cumsum(cache_seqlens, 0, dtype=torch.int32, out=cu_k[1:])
+        gathered = ops.mla_kv_gather(kv_cache, block_table, cu_k, int(total_keys), out=gathered)
+        if not (q.stride(-1) == 1 and q.stride(0) % 8 == 0 and q.stride(1) % 8 == 0 and q.data_ptr() % 16 == 0):
+            q = q.contiguous()
+        cu_q = cu_seqlens_q.to(device=dev, dtype=torch.int32).contiguous()
+        out = torch.empty(T, H, C, dtype=torch.bfloat16, device=dev)
+        check(
+            _lib.lib().chitu_ext2_mla_prefill_flash_continue(
+                ptr(q), i64(q.stride(0)), i64(q.stride(1)), ptr(gathered), i64(gathered.stride(0)), ptr(cu_q), ptr(cu_k), i32(n_seq),
+                i32(int(max_seqlen_q)), f32(softmax_scale), ptr(out), i32(H), i32(C), i32(R), stream_ptr(),
+            ),
+            "mla_prefill_flash_continue",
+        )
+        return out
+
     # ------------------------------------------------------------------ GQA / MHA continued prefill over the paged cache
     def attn_varlen_with_kvcache(self, q, k_cache, v_cache, cu_seqlens_q, cache_seqlens, block_table, max_seqlen_q, causal=True,
                                  window_size=(-1, -1), softcap=0.0, softmax_scale=None):

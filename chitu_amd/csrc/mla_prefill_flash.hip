@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "lds_dma.h"
+#include "chitu_hip_ext2.h"
 
 namespace chitu {
 
@@ -125,9 +126,22 @@ constexpr int kRing = 4;                     // 155648 B
 constexpr int kPieces = 9;                   // LDS-DMA pieces per wave and block: 8 latent rows + 8 rope rows
 }  // namespace pfp
 
+// kCont (chitu_ext2_mla_prefill_flash_continue): separate query and key extents, the causal mask aligned bottom-right
+// (chitu/attn_backend.py:39-90 with seqlen_q != seqlen_k).  Sequence `seq` has n = cu_seqlens[seq + 1] - cu_seqlens[seq] query
+// rows and L = cu_seqlens_k[seq + 1] - cu_seqlens_k[seq] >= n key rows; the queries are the LAST n positions, P = L - n .. L - 1.
+// Query blocks stay aligned to ABSOLUTE positions: workgroup x owns positions p0 .. p0 + 7 with p0 = 8 (P / 8) + 8 x', so its
+// eight queries never straddle a 32-key block and "only the last key block is masked" (iter's LAST) holds for every prefix --
+// blocks that started at the first new token would, for P % 8 != 0, leave the earlier of two key blocks unmasked.  Rows of the
+// first block below P are dead: they load the first live row's Q and store nothing.  n_keys, nb, pq and the mask are absolute,
+// so everything below the index arithmetic is the kCont = false kernel unchanged; at P = 0 the two are bit-identical, and at any
+// P every workgroup without dead rows computes exactly what the whole-sequence call computes for those rows.
+// L < n is outside the contract (P clamps to 0: the last L query rows are computed, the first n - L are not written).
+// kCont = false ignores cu_seqlens_k and compiles to the same instructions as the kernel without the template.
+template <bool kCont>
 __global__ __launch_bounds__(256, 1) void mla_prefill_flash_pipe_kernel(
     const bf16_t* __restrict__ q, int64_t q_st, int64_t q_sh, const bf16_t* __restrict__ kv, int64_t kv_st,
-    const int32_t* __restrict__ cu_seqlens, float scale, bf16_t* __restrict__ out, int H) {
+    const int32_t* __restrict__ cu_seqlens, float scale, bf16_t* __restrict__ out, int H,
+    const int32_t* __restrict__ cu_seqlens_k) {
     using namespace pff;
     using namespace pfp;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -135,14 +149,28 @@ __global__ __launch_bounds__(256, 1) void mla_prefill_flash_pipe_kernel(
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int row = lane & 31, hi = lane >> 5;
     const int seq = blockIdx.y, h0 = blockIdx.z * 16;
-    const int s0 = cu_seqlens[seq], L = cu_seqlens[seq + 1] - s0;
-    const int p0 = ((int)gridDim.x - 1 - (int)blockIdx.x) * kBQ;  // heaviest (latest) block first
+    // s0: first key row; L: keys; q_off: Q / out row of absolute position 0; p_lo: first live position (the prefix length)
+    int s0, L, q_off, p_lo, p0;
+    if constexpr (kCont) {
+        const int sq = cu_seqlens[seq], n = cu_seqlens[seq + 1] - sq;
+        s0 = cu_seqlens_k[seq];
+        L = cu_seqlens_k[seq + 1] - s0;
+        p_lo = max(L - n, 0);
+        q_off = sq - (L - n);
+        p0 = (p_lo / kBQ + (int)gridDim.x - 1 - (int)blockIdx.x) * kBQ;
+        if (n <= 0) return;
+    } else {
+        s0 = cu_seqlens[seq], L = cu_seqlens[seq + 1] - s0;
+        q_off = s0, p_lo = 0;
+        p0 = ((int)gridDim.x - 1 - (int)blockIdx.x) * kBQ;  // heaviest (latest) block first
+    }
     if (p0 >= L) return;
     const int nq = min(kBQ, L - p0);
+    const int t_lo = kCont ? max(p_lo - p0, 0) : 0;  // first live query of this block (0 but in the block that holds position P)
     const int n_keys = p0 + nq;
     const int nb = (n_keys + kKeys - 1) / kKeys;  // key blocks 0 .. nb - 1; only the last one reaches into the block's own tokens
     const int tq = 2 * wave + (row >> 4);
-    const int pq = p0 + min(tq, nq - 1);
+    const int pq = p0 + (kCont ? max(min(tq, nq - 1), t_lo) : min(tq, nq - 1));
     const int head = min(h0 + (row & 15), H - 1);
     const bf16_t* kbase = kv + (int64_t)s0 * kv_st;
     const uint32_t lds0 = lds_offset_of(smem);
@@ -169,7 +197,7 @@ __global__ __launch_bounds__(256, 1) void mla_prefill_flash_pipe_kernel(
 
     s16x8 qf[36];
     {
-        const bf16_t* qp = q + (int64_t)(s0 + pq) * q_st + (int64_t)head * q_sh + hi * 8;
+        const bf16_t* qp = q + (int64_t)(q_off + pq) * q_st + (int64_t)head * q_sh + hi * 8;
 #pragma unroll
         for (int kk = 0; kk < 36; ++kk) qf[kk] = *reinterpret_cast<const s16x8*>(qp + kk * 16);
 #pragma unroll
@@ -331,8 +359,11 @@ __global__ __launch_bounds__(256, 1) void mla_prefill_flash_pipe_kernel(
     for (int r = 0; r < 32; ++r) {
         const int t = 2 * wave + (r >> 4), h = h0 + (r & 15);
         if (t >= nq || h >= H) continue;  // wave-uniform
+        if constexpr (kCont) {
+            if (t < t_lo) continue;  // a dead row of the block that holds position P
+        }
         const i32x4 v = *reinterpret_cast<const i32x4*>(ostage + r * kORow + lane * 16);
-        *reinterpret_cast<i32x4*>(out + ((int64_t)(s0 + p0 + t) * H + h) * kC + lane * 8) = v;
+        *reinterpret_cast<i32x4*>(out + ((int64_t)(q_off + p0 + t) * H + h) * kC + lane * 8) = v;
     }
 }
 
@@ -351,10 +382,32 @@ extern "C" int chitu_hip_mla_prefill_flash(const void* q_bf16, int64_t q_stride_
     if (n_seq == 0 || max_seqlen == 0) return CHITU_OK;
     const size_t lds = (size_t)pfp::kRing * pfp::kSlot;
     // (set on every call: the opt-in is per device, a process-wide "done" flag would skip the second GPU of a multi-device process)
-    (void)hipFuncSetAttribute((const void*)mla_prefill_flash_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)mla_prefill_flash_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const dim3 grid((unsigned)((max_seqlen + pff::kBQ - 1) / pff::kBQ), (unsigned)n_seq, (unsigned)((heads + 15) / 16));
-    hipLaunchKernelGGL(mla_prefill_flash_pipe_kernel, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q_bf16, q_stride_t,
+    hipLaunchKernelGGL(mla_prefill_flash_pipe_kernel<false>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q_bf16, q_stride_t,
                        q_stride_h, (const bf16_t*)kv_bf16, kv_stride_t, cu_seqlens, softmax_scale, (bf16_t*)out_bf16,
-                       (int)heads);
+                       (int)heads, (const int32_t*)nullptr);
+    CHITU_RETURN_LAUNCH_STATUS();
+}
+
+// chitu_hip_ext2.h: the same kernel with separate query and key extents (kCont).  One workgroup column more than
+// ceil(max_seqlen_q / 8): the first block of a sequence starts at 8 (P / 8), up to 7 positions in front of its first query.
+extern "C" int chitu_ext2_mla_prefill_flash_continue(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h,
+                                                     const void* kv_bf16, int64_t kv_stride_t, const int32_t* cu_seqlens_q,
+                                                     const int32_t* cu_seqlens_k, int32_t n_seq, int32_t max_seqlen_q,
+                                                     float softmax_scale, void* out_bf16, int32_t heads, int32_t kv_lora_rank,
+                                                     int32_t rope_dim, void* stream) {
+    using namespace chitu;
+    CHITU_REQUIRE(q_bf16 && kv_bf16 && cu_seqlens_q && cu_seqlens_k && out_bf16 && n_seq >= 0 && max_seqlen_q >= 0 && heads >= 1);
+    if (kv_lora_rank != pff::kC || rope_dim != pff::kR) return CHITU_ERR_UNSUPPORTED;
+    CHITU_REQUIRE(q_stride_t % 8 == 0 && q_stride_h % 8 == 0 && kv_stride_t % 8 == 0);
+    CHITU_REQUIRE(((uintptr_t)q_bf16 | (uintptr_t)kv_bf16 | (uintptr_t)out_bf16) % 16 == 0);
+    if (n_seq == 0 || max_seqlen_q == 0) return CHITU_OK;
+    const size_t lds = (size_t)pfp::kRing * pfp::kSlot;
+    (void)hipFuncSetAttribute((const void*)mla_prefill_flash_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const dim3 grid((unsigned)((max_seqlen_q + pff::kBQ - 1) / pff::kBQ + 1), (unsigned)n_seq, (unsigned)((heads + 15) / 16));
+    hipLaunchKernelGGL(mla_prefill_flash_pipe_kernel<true>, grid, dim3(256), lds, (hipStream_t)stream, (const bf16_t*)q_bf16,
+                       q_stride_t, q_stride_h, (const bf16_t*)kv_bf16, kv_stride_t, cu_seqlens_q, softmax_scale, (bf16_t*)out_bf16,
+                       (int)heads, cu_seqlens_k);
     CHITU_RETURN_LAUNCH_STATUS();
 }

@@ -387,7 +387,21 @@ class AttentionDeepSeekV3(torch.nn.Module):
         kv_cache_dtype "fp8": the rows are quantised (ops.mla_kv_quant_fp8) on their way into the pages; the prompt's own
         attention below keeps reading the unquantised rows, as other engines with an fp8 KV cache do -- only later decode
         steps see the quantised prompt."""
+        if getattr(varlens, "continued", False):  # (set by DeepSeekV3Decoder.prefill_continue)
+            return self.prefill_forward_paged(x_quant, cos, sin, varlens)
         H, C, R = self.n_local_heads, self.kv_lora_rank, self.qk_rope_head_dim
+        T = x_quant[0].shape[0]
+        q_abs, q_pe, kv_c, kv_pe = self._prefill_projections(x_quant, cos, sin)
+        self.cache.finalize_cache_bylayer_prefill(ops.mla_kv_quant_fp8(kv_pe) if self.kv_fp8 else kv_pe, None,
+                                                  self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
+        o = self.attn_backend.attn_varlen_func(
+            torch.cat([q_abs, q_pe], dim=-1), kv_pe.view(T, 1, C + R), kv_c.view(T, 1, C), varlens.prefix_lens,
+            varlens.prefix_lens, varlens.max_len, varlens.max_len, causal=True, softmax_scale=self.softmax_scale)
+        return self._prefill_output(o)
+
+    def _prefill_projections(self, x_quant, cos, sin):
+        """The projections both prefill forms share: (q_abs [T, H, C], rotated q_pe [T, H, R], kv_c [T, C], kv_pe [T, C + R])."""
+        H, C = self.n_local_heads, self.kv_lora_rank
         T = x_quant[0].shape[0]
         if self.q_lora_rank > 0:
             q_a_kv = self.wqkv_a(None, x_quant=x_quant)  # [T, q_lora + C + R]
@@ -402,16 +416,34 @@ class AttentionDeepSeekV3(torch.nn.Module):
         kv_c = ops.rms_norm(q_a_kv[:, ql : ql + C], self.kv_norm.weight, self.kv_norm.eps)
         q_pe, k_pe = ops.apply_rotary_pos_emb(q_pe, q_a_kv[:, ql + C :], cos, sin, rotary_type="llama")
         kv_pe = torch.cat([kv_c, k_pe], dim=-1)  # [T, C + R]
-        self.cache.finalize_cache_bylayer_prefill(ops.mla_kv_quant_fp8(kv_pe) if self.kv_fp8 else kv_pe, None,
-                                                  self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
         nblk = C // BLOCK
         q_abs = ops.absorb_bmm_fp8(q_nope, self.w_uk_transposed(), self.wkv_b.scale, 0, 2 * nblk, 1, 0)
-        o = self.attn_backend.attn_varlen_func(
-            torch.cat([q_abs, q_pe], dim=-1), kv_pe.view(T, 1, C + R), kv_c.view(T, 1, C), varlens.prefix_lens,
-            varlens.prefix_lens, varlens.max_len, varlens.max_len, causal=True, softmax_scale=self.softmax_scale)
+        return q_abs, q_pe, kv_c, kv_pe
+
+    def _prefill_output(self, o):
+        """out = o . W_UV^T + the act-quant of wo's input, then wo."""
+        H, C = self.n_local_heads, self.kv_lora_rank
+        nblk = C // BLOCK
         w_uv = self.wkv_b.weight.view(H, self.qk_nope_head_dim + self.v_head_dim, C)[:, self.qk_nope_head_dim :]
         oq, os_ = ops.absorb_uv_quant_fp8(o, w_uv, self.wkv_b.scale, nblk, 2 * nblk, 1)
         return self.wo(None, x_quant=(oq, os_))
+
+    def prefill_forward_paged(self, x_quant, cos, sin, varlens):
+        """prefill_forward for tokens behind rows that are already cached (PagedKVCacheManager.prepare_cache_prefill_continue
+        has run; no reference counterpart): the same projections, RoPE at the absolute positions (cos / sin rows), the new latent
+        rows scattered into their pages (quantised first with an fp8 cache), then the attention over the pages
+        (HipAttnBackend.mla_attn_varlen_with_kvcache: gather + flash kernel) -- every query sees the cached prefix and the new
+        rows up to itself.  varlens.gathered / varlens.total_keys: the gather buffer all layers share and the host-known key
+        count (DeepSeekV3Decoder.prefill_continue).
+        kv_cache_dtype "fp8": everything is read back from the pages, so a chunk attends over the QUANTISED rows of its prefix
+        and of itself, where one-shot prefill attends over the unquantised rows of the prompt."""
+        q_abs, q_pe, _, kv_pe = self._prefill_projections(x_quant, cos, sin)
+        self.cache.finalize_cache_bylayer_prefill_continue(ops.mla_kv_quant_fp8(kv_pe) if self.kv_fp8 else kv_pe, None, self.layer_id)
+        o = self.attn_backend.mla_attn_varlen_with_kvcache(
+            torch.cat([q_abs, q_pe], dim=-1), self.cache.get_paged_kv_cache(self.layer_id), varlens.prefix_lens,
+            self.cache.get_gpu_continue_seq_lens_incl(), self.cache.get_gpu_continue_block_table(), varlens.max_len,
+            varlens.total_keys, self.softmax_scale, gathered=varlens.gathered)
+        return self._prefill_output(o)
 
 
 class MLPDeepSeekV3(torch.nn.Module):
@@ -689,10 +721,28 @@ class DeepSeekV3Decoder(torch.nn.Module):
         return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
 
     @torch.inference_mode()
-    def prefill(self, tokens, req_ids):
+    def prefill(self, tokens, req_ids, chunk_size=None):
         """tokens: list of per-request token-id lists; req_ids: their cache keys.  Runs the prompt
         through every layer, fills the KV pages, returns fp32 logits [n_req, vocab] of each prompt's
-        LAST token (prefill_single_device, model.py:451-465).  Eager launches."""
+        LAST token (prefill_single_device, model.py:451-465).  Eager launches.
+        chunk_size = c: the first c tokens of every prompt run here, the rest in rounds of prefill_continue with at most c tokens
+        per request (a request whose prompt is exhausted leaves the later rounds), so no round holds more than n_req * c rows
+        (LlamaDecoder.prefill's rule).  With kv_cache_dtype "fp8" the later chunks attend over quantised rows (prefill_continue)."""
+        if chunk_size is not None:
+            c = int(chunk_size)
+            if c < 1:
+                raise ValueError(f"chunk_size={chunk_size}: at least one token per round")
+            req_ids = list(req_ids)
+            logits = self.prefill([list(t[:c]) for t in tokens], req_ids)
+            done = c
+            while True:
+                live = [i for i, t in enumerate(tokens) if len(t) > done]
+                if not live:
+                    return logits
+                out = self.prefill_continue([list(tokens[i][done : done + c]) for i in live], [req_ids[i] for i in live])
+                logits[torch.tensor(live, device=logits.device)] = out  # a later round overwrites it until the prompt ends
+                done += c
+
         from . import graphs
 
         graphs.sweep_if_memory_was_recycled()  # the eager path's canary: once after an xGMI communicator came or went
@@ -703,19 +753,61 @@ class DeepSeekV3Decoder(torch.nn.Module):
         h, pending = self.embed(flat), None
         for layer in self.layers:
             h, pending = layer(h, pending, cos, sin, varlens)
+        self.cache.finalize_cache_all_prefill(req_ids, varlens)
+        return self._last_token_logits(h, pending, varlens)
+
+    def _last_token_logits(self, h, pending, varlens):
+        """The final norm and the head on the last row of every sequence of a prefill call."""
         last = torch.tensor([p - 1 for p in varlens.cpu_prefix_lens[1:]], dtype=torch.int64, device=self.device)
         h = h[last]
         pending = tp.resolve(pending)
         if pending is not None:
             pending = pending[last].contiguous()
         h = add_norm(h, pending, self.norm)[1]
-        self.cache.finalize_cache_all_prefill(req_ids, varlens)
         return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
 
     @torch.inference_mode()
+    def prefill_continue(self, tokens, req_ids):
+        """Ragged chunks of new tokens for requests that are already cached (a conversation's next turn, the next chunk of a
+        long prompt, a draft model's catch-up) -> fp32 logits [n_req, vocab] of each chunk's last token; appends their latent
+        rows.  Positions, and so cos / sin, continue from each request's cached length.  The attention reads the pages
+        (AttentionDeepSeekV3.prefill_forward_paged: one gather + one flash launch per layer, the gather buffer allocated here
+        once and shared by the layers); everything else is prefill's stack on the new rows, tensor- and expert-parallel paths
+        included.  An unknown request, a chunk that overruns the rotary table or the block table, or too few free pages raises
+        before any cache state changes.
+        kv_cache_dtype "fp8": the chunk attends over the quantised rows of its prefix AND of itself (everything is read back
+        from the pages), where one-shot prefill attends over the unquantised prompt -- the numbers of a chunked fp8 prefill are
+        those of prefill + token-by-token decode, not those of the one-shot call."""
+        from . import graphs
+
+        req_ids = list(req_ids)
+        assert len(tokens) == len(req_ids) and all(len(t) >= 1 for t in tokens)
+        for r, t in zip(req_ids, tokens):
+            if r not in self.cache.seq_lens:
+                raise KeyError(f"request {r!r} is not cached: a continued prefill extends a sequence that prefill registered")
+            assert self.cache.seq_lens[r] + len(t) <= self.cos_table.shape[0], \
+                f"request {r!r}: {self.cache.seq_lens[r]} + {len(t)} tokens exceed max_position_embeddings={self.cos_table.shape[0]}"
+        graphs.sweep_if_memory_was_recycled()
+        varlens = VarLens(tokens, self.device)
+        varlens.continued = True
+        self.cache.prepare_cache_prefill_continue(req_ids, varlens)
+        varlens.total_keys = sum(self.cache.seq_lens[r] + len(t) for r, t in zip(req_ids, tokens))
+        varlens.gathered = torch.empty(varlens.total_keys, self.args.kv_lora_rank + self.args.qk_rope_head_dim, dtype=torch.bfloat16,
+                                       device=self.device)
+        pos = self.cache.get_continue_position_ids()
+        flat = torch.tensor([t for seq in tokens for t in seq], dtype=torch.int64, device=self.device)
+        cos, sin = self.cos_table[pos], self.sin_table[pos]
+        h, pending = self.embed(flat), None
+        for layer in self.layers:
+            h, pending = layer(h, pending, cos, sin, varlens)
+        self.cache.finalize_cache_all_prefill_continue(req_ids)
+        return self._last_token_logits(h, pending, varlens)
+
+    @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, req_ids=None, use_graph=True, temperatures=None, top_ks=None,
-                 top_ps=None, frequency_penalties=None, generator=None):
-        """Prefill, then max_new_tokens - 1 decode steps; returns [n_req, max_new_tokens] int64 and frees the
+                 top_ps=None, frequency_penalties=None, generator=None, prefill_chunk_size=None):
+        """Prefill (prefill_chunk_size: in chunks, prefill's chunk_size), then max_new_tokens - 1 decode steps; returns
+        [n_req, max_new_tokens] int64 and frees the
         requests' pages.  Token selection is executor.py:82-112 on the device (chitu_amd.sampling): greedy
         unless some top_k > 1 (then per-request temperature / top-k / top-p sampling, uniforms from
         `generator`), with an optional per-request frequency penalty; tokens never visit the host."""
@@ -724,7 +816,8 @@ class DeepSeekV3Decoder(torch.nn.Module):
         req_ids = [f"gen{i}" for i in range(len(prompts))] if req_ids is None else list(req_ids)
         pick = DeviceSampler(len(prompts), max_new_tokens, self.device, temperatures, top_ks, top_ps,
                              frequency_penalties, generator)
-        tok = pick(self.prefill(prompts, req_ids))
+        tok = pick(self.prefill(prompts, req_ids) if prefill_chunk_size is None else
+                   self.prefill(prompts, req_ids, chunk_size=prefill_chunk_size))
         out = [tok]
         for _ in range(max_new_tokens - 1):
             self.cache.prepare_cache_decode(req_ids)

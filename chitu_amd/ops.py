@@ -267,6 +267,41 @@ def mla_kv_dequant_fp8(rows):
     return out
 
 
+def mla_kv_gather(kv_cache, block_table, cu_seqlens_k, total_rows, out=None):
+    """The rows of ragged sequences out of one layer of the paged latent KV cache, contiguous: out[cu_seqlens_k[s] + t] = row t of
+    sequence s = kv_cache[block_table[s][t // page]][t % page] for t < cu_seqlens_k[s + 1] - cu_seqlens_k[s], as bf16 [.., 576].
+    kv_cache: bf16 [pages, page, 576] (rows copied) or the fp8 cache uint8 [pages, page, 656] (attn_backend.is_fp8_mla_cache:
+    rows widened exactly as mla_kv_dequant_fp8 widens them).  cu_seqlens_k int32 [n_seq + 1] on the device; total_rows =
+    cu_seqlens_k[-1], given by the host (no sync).  out: bf16 [>= total_rows, 576] rows to fill (row stride a multiple of 8
+    elements); rows beyond total_rows are left alone.  A table entry outside [0, pages) gives a row of zeros; rows beyond a
+    sequence's length and pages no sequence names are never read (chitu_ext2_mla_kv_gather)."""
+    from .attn_backend import is_fp8_mla_cache
+
+    require_cuda(kv_cache, block_table, cu_seqlens_k, out)
+    fp8 = is_fp8_mla_cache(kv_cache)
+    assert kv_cache.dim() == 3 and kv_cache.is_contiguous() and (fp8 or (kv_cache.dtype == torch.bfloat16 and kv_cache.shape[-1] == 576))
+    assert block_table.dtype == torch.int32 and block_table.dim() == 2
+    block_table = block_table.contiguous()  # (the entry takes one number for the table's width and its row stride)
+    assert cu_seqlens_k.dtype == torch.int32 and cu_seqlens_k.dim() == 1 and cu_seqlens_k.is_contiguous()
+    n_seq = cu_seqlens_k.numel() - 1
+    total_rows = int(total_rows)
+    assert n_seq >= 0 and block_table.shape[0] >= n_seq and total_rows >= 0
+    if out is None:
+        out = torch.empty(total_rows, 576, dtype=torch.bfloat16, device=kv_cache.device)
+    assert out.dtype == torch.bfloat16 and out.dim() == 2 and out.shape[0] >= total_rows and out.shape[1] == 576 and out.stride(1) == 1
+    if total_rows == 0 or n_seq == 0:
+        return out
+    check(
+        _lib.lib().chitu_ext2_mla_kv_gather(
+            ptr(kv_cache), i32(1 if fp8 else 0), i64(kv_cache.shape[0]), i32(kv_cache.shape[1]), ptr(block_table),
+            i32(block_table.stride(0)), ptr(cu_seqlens_k), i32(n_seq), i64(total_rows), ptr(out), i64(out.stride(0)), i32(512), i32(64),
+            stream_ptr(),
+        ),
+        "mla_kv_gather",
+    )
+    return out
+
+
 def append_mla_kv_fp8(kv_cache, page_table, this_kv, old_seq_lens):
     """append_to_paged_kv_cache for the fp8 latent cache: row i of this_kv (bf16 [bs, 576] or [bs, 1, 576]) is quantised
     (mla_kv_quant_fp8's bytes) into kv_cache[page_table[i][L_i // page]][L_i % page], kv_cache uint8 [pages, page, 656].
