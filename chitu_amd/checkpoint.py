@@ -543,6 +543,57 @@ def load_checkpoint_hf_llama(model, path: str, rank: int = 0, world: int = 1, sk
     load_deepseek_v3(model, st)  # the generic strict, shape- and dtype-checked in-place copy
 
 
+_QWEN3_MOE_EXPERT = re.compile(r"(?:model\.)?(layers\.\d+)\.mlp\.experts\.(\d+)\.(gate_proj|up_proj|down_proj)\.weight$")
+
+
+def preprocess_hf_qwen3_moe(state: Mapping[str, torch.Tensor], args, rank: int = 0, world: int = 1) -> Dict[str, torch.Tensor]:
+    """Published Qwen3-MoE names -> this TP rank's Qwen3MoeDecoder parameters.  Attention, norms, embedding, head and the
+    router (`mlp.gate.weight`, whole on every rank) go through the Qwen3 path (preprocess_hf_llama + to_llama_module_names).
+    The experts (`mlp.experts.E.{gate,up,down}_proj.weight`) are sliced by width -- this rank's rows of gate_proj and of
+    up_proj, its columns of down_proj -- and stacked: ffn.w13 [E, 2 I / world, dim] = gate rows, then up rows; ffn.w2
+    [E, dim, I / world]."""
+    rest, experts = {}, {}
+    for k, v in state.items():
+        m = _QWEN3_MOE_EXPERT.match(k)
+        if m:
+            experts.setdefault(m.group(1), {}).setdefault(m.group(3), {})[int(m.group(2))] = v
+        else:
+            rest[k] = v
+    out = to_llama_module_names(preprocess_hf_llama(rest, args.n_heads, args.n_kv_heads, args.dim, rank, world,
+                                                    head_dim=args.head_dim))
+    E = args.num_experts
+    for layer, mats in experts.items():
+        for part in ("gate_proj", "up_proj", "down_proj"):
+            if sorted(mats.get(part, {})) != list(range(E)):
+                raise KeyError(f"{layer}: experts present for {part}: {sorted(mats.get(part, {}))}, expected 0..{E - 1}")
+        cut = lambda part, e, dim: _chunk(mats[part][e], world, rank, dim, f"{layer}.mlp.experts.{e}.{part}.weight")
+        out[f"{layer}.ffn.w13"] = torch.stack([torch.cat([cut("gate_proj", e, 0), cut("up_proj", e, 0)], dim=0) for e in range(E)])
+        out[f"{layer}.ffn.w2"] = torch.stack([cut("down_proj", e, 1) for e in range(E)])
+    return out
+
+
+def load_checkpoint_hf_qwen3_moe(model, path: str, rank: int = 0, world: int = 1) -> None:
+    """HF Qwen3-MoE directory (Qwen3-30B-A3B, Qwen3-235B-A22B: per-expert tensors on disk) -> a Qwen3MoeDecoder built for this
+    TP rank.  load_checkpoint_hf_llama is not involved and keeps its behaviour."""
+    from safetensors import safe_open
+
+    from .qwen3_moe import check_args
+
+    args = model.args
+    check_args(args, world)
+    files = sorted(glob.glob(os.path.join(path, "*.safetensors")))
+    if not files:
+        raise FileNotFoundError(f"no *.safetensors under {path}")
+    state = {}
+    for fp in files:
+        with safe_open(fp, framework="pt", device="cpu") as f:
+            for name in f.keys():
+                state[name] = f.get_tensor(name)
+    if getattr(args, "tie_word_embeddings", False) and "lm_head.weight" not in state:
+        state["lm_head.weight"] = state["model.embed_tokens.weight" if "model.embed_tokens.weight" in state else "embed_tokens.weight"]
+    load_deepseek_v3(model, preprocess_hf_qwen3_moe(state, args, rank, world))  # strict, shape- and dtype-checked in-place copy
+
+
 # Meta-format Llama checkpoints (`consolidated.*.pth` names: tok_embeddings, attention.wq .. wo, feed_forward.w1 .. w3,
 # attention_norm / ffn_norm, output) -- what the reference's TransformerLlama loads (models/model_llama.py:86-99), the class
 # BASELINE config 1 runs.  Its column list spells the embedding "embed", which never matches "tok_embeddings"

@@ -42,6 +42,7 @@ __device__ __forceinline__ int mx_tile_frag_off(int j, int g) { return j * 64 + 
 template <bool SILU>
 struct MoeMxTile : MoeTiledNoProbe {
     static constexpr int kRing = kMxTiledRing, kPieces = 2 + 1;
+    static constexpr bool kActScales = true;
     using Ctx = MoeTileCtx<SILU>;
     uint8_t (*sW)[128 * 64];
     uint32_t (*sE)[4 * 64];

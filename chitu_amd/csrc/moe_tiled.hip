@@ -51,6 +51,7 @@ struct MoeTileScales {  // the weight tile's block scales of a K block (workgrou
 template <bool SILU, int TM>
 struct MoeFp8Tile {
     static constexpr int kRing = moe_ring_of(TM), kPieces = 4;
+    static constexpr bool kActScales = true;
     using Ctx = MoeTileCtx<SILU>;
     uint8_t (*sW)[128 * 128];
     const fp8_t *W, *We;

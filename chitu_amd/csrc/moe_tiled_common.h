@@ -11,6 +11,9 @@
 // A weight format is a small struct F (MoeFp8Tile, MoeMxTile) that owns what differs -- the weight tile's LDS image, where its
 // scales come from, the block product and how it is folded into the accumulator:
 //   F::kRing, F::kPieces        ring stages; DMA pieces per wave and stage that the format brings itself
+//   F::kActScales               the activations are fp8 with one fp32 scale per (row, 128-wide K block) that rides with the tile
+//                               (MoeBf16Tile, moe_bf16_tiled.hip: false -- bf16 activations, a K block is 128 BYTES = 64 elements,
+//                               `K` and `Xq` are then the row length in bytes and the matrix as bytes; sS and Xs are not touched)
 //   f.init(c)                   the expert's base pointers, the wave's staging offsets of the first tile
 //   f.set_w_offsets(c, rep)     ... and of tile `rep` of an NREP walk
 //   f.consume_offsets()         its part of the fence ahead of the first request
@@ -134,10 +137,14 @@ __device__ __forceinline__ void moe_tiled_body(F& f, uint8_t (*sX)[TM * 128], fl
     // piece; the other lanes repeat them into the piece's unused part -- the same number of pieces for every wave keeps the
     // counted wait below one constant).  As plain loads one step ahead they put a vmcnt(0) of the compiler's into the MFMA
     // stream (fp8_gemm_tiled.hip).
-    const uint32_t soff = (uint32_t)((min(sorted_ids[mb * TM + wave * (TM / 4) + (lane & (TM / 4 - 1))], numel - 1) / row_div) * KB * 4);
-    const uint32_t ldsX = lds_offset_of(&sX[0][0]), ldsS = lds_offset_of(&sS[0][0]);
+    uint32_t soff = 0, ldsS = 0;
+    if constexpr (F::kActScales) {
+        soff = (uint32_t)((min(sorted_ids[mb * TM + wave * (TM / 4) + (lane & (TM / 4 - 1))], numel - 1) / row_div) * KB * 4);
+        ldsS = lds_offset_of(&sS[0][0]);
+    }
+    const uint32_t ldsX = lds_offset_of(&sX[0][0]);
 
-    constexpr int kPieces = F::kPieces + XP + 1;  // DMA pieces per wave and stage
+    constexpr int kPieces = F::kPieces + XP + (F::kActScales ? 1 : 0);  // DMA pieces per wave and stage
     auto issue = [&](int stage, int kb) {
         const uint32_t b = (uint32_t)stage;
         f.issue_weights(c, b, kb);
@@ -145,7 +152,7 @@ __device__ __forceinline__ void moe_tiled_body(F& f, uint8_t (*sX)[TM * 128], fl
         for (int i = 0; i < XP; ++i)
             glds16_sbase(uniform_ptr(Xq + (size_t)kb * 128), xoff[i], ldsX + b * (TM * 128) + (uint32_t)((wave * XP + i) * 1024));
         f.issue_weight_scales(c, b, kb);
-        glds4_sbase(uniform_ptr(Xs + kb), soff, ldsS + b * 1024 + (uint32_t)(wave * 256));
+        if constexpr (F::kActScales) glds4_sbase(uniform_ptr(Xs + kb), soff, ldsS + b * 1024 + (uint32_t)(wave * 256));
     };
     const int xfoff = kblock_frag_off(j, g);  // this lane's activation fragment inside a 16-slot tile (second half: ^ 64)
 
@@ -231,7 +238,7 @@ __device__ __forceinline__ void moe_tiled_body(F& f, uint8_t (*sX)[TM * 128], fl
     for (int i = 0; i < XP; ++i) asm volatile("" ::"v"(xoff[i]));
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) asm volatile("" ::"v"(rw[mt]), "v"(slot[mt]));
-    asm volatile("" ::"v"(soff));
+    if constexpr (F::kActScales) asm volatile("" ::"v"(soff));
     issue_next();
     if (R == 3 && steps > 1) issue_next();
     f.first_scales(c);
@@ -255,7 +262,8 @@ __device__ __forceinline__ void moe_tiled_body(F& f, uint8_t (*sX)[TM * 128], fl
             const uint8_t* xr = &sX[buf][mt * 16 * 128];
             const i32x4 xb0 = *reinterpret_cast<const i32x4*>(xr + xfoff), xb1 = *reinterpret_cast<const i32x4*>(xr + (xfoff ^ 64));
             // wave w's scale piece holds slots (TM / 4) w ..: sub-tile mt's 16 values sit in piece mt / (TM / 64) at (mt % (TM / 64)) * 16
-            const float sc = sS[buf][(mt / (TM / 64)) * 64 + (mt % (TM / 64)) * 16 + j];
+            float sc = 1.f;
+            if constexpr (F::kActScales) sc = sS[buf][(mt / (TM / 64)) * 64 + (mt % (TM / 64)) * 16 + j];
             f.fold(acc[0][mt], acc[1][mt], xb0, xb1, sc);
         }
         F::mark_fold(acc[1][0][3]);

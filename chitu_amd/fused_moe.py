@@ -155,6 +155,10 @@ _MOE_TILED_BLOCK_M = int(os.environ.get("CHITU_MOE_TILED_BLOCK_M", "128"))
 # us per layer, streaming / tiled: 128 tokens 195 / 263, 256: 228 / 277, 384: 273 / 286, 512: 355 / 299, 1024: 592 / 369, 2048: 1068 / 481 --
 # 512 is the smallest measured count at which the tiled form wins.  (The per-expert floor above still applies.)
 _MOE_MXFP4_TILED_MIN_TOKENS = int(os.environ.get("CHITU_MOE_MXFP4_TILED_MIN_TOKENS", "512"))
+# bf16 experts (csrc/moe_bf16_tiled.hip): 0 = never for generic fused_experts(use_fp8_w8a8=False) calls, whose callers and tests
+# were built on the streaming form; a model opts in per call (fused_experts(bf16_tiled_min_tokens=...): the Qwen3-MoE block,
+# chitu_amd/qwen3_moe.py, which carries the measured floor).  (The per-expert floor above still applies.)
+_MOE_BF16_TILED_MIN_TOKENS = int(os.environ.get("CHITU_MOE_BF16_TILED_MIN_TOKENS", "0"))
 
 
 
@@ -202,6 +206,7 @@ def fused_experts(
     reduce_topk: bool = True,
     use_int8_w8a8: bool = False,
     aligned=None,
+    bf16_tiled_min_tokens: Optional[int] = None,
     use_mxfp4_w4a8: bool = False,
 ) -> torch.Tensor:
     """Same signature as chitu/fused_moe.py:1060-1127 (+ optional a1_quant / reduce_topk, see fused_experts_impl).  (The reference's inplace=False branch
@@ -211,6 +216,7 @@ def fused_experts(
         use_int8_w8a16, use_int4_w4a16, global_num_experts, expert_map, w1_scale, w2_scale, w1_zp,
         w2_zp, a1_scale, a2_scale, block_shape, soft_fp8=soft_fp8, a1_quant=a1_quant, reduce_topk=reduce_topk,
         use_int8_w8a8=use_int8_w8a8, aligned=aligned, use_mxfp4_w4a8=use_mxfp4_w4a8,
+        bf16_tiled_min_tokens=bf16_tiled_min_tokens,
     )
 
 
@@ -239,6 +245,7 @@ def fused_experts_impl(
     reduce_topk: bool = True,
     use_int8_w8a8: bool = False,
     aligned=None,
+    bf16_tiled_min_tokens: Optional[int] = None,
     use_mxfp4_w4a8: bool = False,
 ):
     """out[t] = sum_j w[t,j] * W2[e_tj] . (silu(W1[e_tj] x_t)[:I] * (W1[e_tj] x_t)[I:])
@@ -258,6 +265,8 @@ def fused_experts_impl(
     (ops.gate_deepseek_v3(align=...): routing and sort in one launch) -- skips the align launch.
     use_mxfp4_w4a8=True: OCP MXFP4 expert weights (packed e2m1 + E8M0 block scales) with the fp8 path's activations and
     rounding points -- `_fused_experts_mxfp4`.
+    bf16_tiled_min_tokens: bf16 experts only -- the token count from which the call takes the compute-shaped grouped GEMMs
+    (csrc/moe_bf16_tiled.hip); None = the module's _MOE_BF16_TILED_MIN_TOKENS (0: never), see `_fused_experts_bf16_act`.
     """
     if use_mxfp4_w4a8:  # before the hidden-size assert: here w1.shape[2] is K/2
         if activation != "silu":
@@ -284,7 +293,8 @@ def fused_experts_impl(
     if not use_fp8_w8a8 or soft_fp8:
         return _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts,
                                        expert_map, w1_scale if use_fp8_w8a8 else None,
-                                       w2_scale if use_fp8_w8a8 else None, block_shape, reduce_topk, aligned)
+                                       w2_scale if use_fp8_w8a8 else None, block_shape, reduce_topk, aligned,
+                                       bf16_tiled_min_tokens)
     assert block_shape is not None and list(block_shape) == [128, 128], "block_shape must be [128, 128]"
     assert w1_scale is not None and w2_scale is not None
     assert a1_scale is None and a2_scale is None, "dynamic per-token-group activation scales only"
@@ -640,11 +650,14 @@ def _fused_experts_int8(hidden_states, w1, w2, topk_weights, topk_ids, inplace, 
 
 
 def _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, expert_map,
-                            w1_scale, w2_scale, block_shape, reduce_topk, aligned):
+                            w1_scale, w2_scale, block_shape, reduce_topk, aligned, tiled_min_tokens=None):
     """bf16 activations: bf16 experts (w*_scale None; use_fp8_w8a8=False, fused_moe.py:298) or fp8 experts decoded to
     bf16 in registers (soft_fp8=True, fused_moe.py:232-276).  align(16) -> grouped GEMM1 with SiluAndMul in its epilogue
     -> grouped GEMM2 (x routed weight) -> top-k sum: the reference's four steps (fused_moe.py:1230-1305) with its
-    rounding points (bf16 after each GEMM, SiluAndMul on bf16 tensors), no activation quantisation."""
+    rounding points (bf16 after each GEMM, SiluAndMul on bf16 tensors), no activation quantisation.
+    bf16 experts, prefill-sized calls (`_takes_tiled` from tiled_min_tokens tokens on; None = _MOE_BF16_TILED_MIN_TOKENS, 0 = never):
+    align(_MOE_TILED_BLOCK_M) -> GEMM1 + silu*mul tiled -> GEMM2 tiled -> sum (csrc/moe_bf16_tiled.hip), the same rounding
+    points with fp32 accumulation across the whole K in another order.  Soft-fp8 experts keep the streaming form."""
     soft = w1_scale is not None
     assert hidden_states.dtype == torch.bfloat16, "bf16 activations"
     if soft:
@@ -671,8 +684,11 @@ def _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inpla
     numel = num_tokens * topk
     topk_ids = topk_ids.contiguous()
     topk_weights = topk_weights.contiguous()
-    cap = numel + global_num_experts * (_MOE_BLOCK_M - 1)
-    nblk = ceil_div(cap, _MOE_BLOCK_M)
+    floor = _MOE_BF16_TILED_MIN_TOKENS if tiled_min_tokens is None else int(tiled_min_tokens)
+    tiled = not soft and _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, min_tokens=floor)
+    block_m = _MOE_TILED_BLOCK_M if tiled else _MOE_BLOCK_M
+    cap = numel + global_num_experts * (block_m - 1)
+    nblk = ceil_div(cap, block_m)
     rnd = lambda n: (n + 255) // 256 * 256
     sizes = [("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
              ("h", numel * I * 2), ("c3", numel * Nout * 2)]
@@ -689,7 +705,7 @@ def _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inpla
     if aligned is None:
         emap = _expert_map_i32(expert_map, global_num_experts, dev)
         check(lib.chitu_hip_moe_align_block_size_mapped(ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel),
-                                                        i32(global_num_experts), i32(_MOE_BLOCK_M), P("sorted"), i64(cap),
+                                                        i32(global_num_experts), i32(block_m), P("sorted"), i64(cap),
                                                         P("experts"), i64(nblk), P("npost"), P("cumsum"), i32(1), ptr(emap), st),
               "moe_align_block_size")
         sorted_p, experts_ptr, npost_p = P("sorted"), P("experts"), P("npost")
@@ -699,6 +715,20 @@ def _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inpla
         assert a_sorted.numel() == cap and a_experts.numel() == nblk, "aligned buffers must come from block 16 over global_num_experts"
         sorted_p, experts_ptr, npost_p = ptr(a_sorted), ptr(a_experts), ptr(a_npost)
     kind = i32(1 if soft else 0)
+    if tiled:
+        # prefill: GEMM1 + SiLU-and-mul tiled, GEMM2 tiled (csrc/moe_bf16_tiled.hip); h stays bf16, nothing is quantised
+        assert nblk <= 65535
+        check(lib.chitu_ext3_moe_gemm1_silu_bf16_tiled(ptr(hidden_states), ptr(w1), sorted_p, experts_ptr, npost_p, P("h"),
+                                                       i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), i32(block_m), st),
+              "moe bf16 gemm1 (tiled, silu fused)")
+        check(lib.chitu_ext3_moe_gemm2_bf16_tiled(P("h"), ptr(w2), sorted_p, experts_ptr, npost_p, ptr(topk_weights),
+                                                  i32(float_dtype_code(topk_weights.dtype)), i32(1), P("c3"), i64(numel), i64(Nout),
+                                                  i64(I), i64(max_mblocks), i32(block_m), st), "moe bf16 gemm2 (tiled)")
+        if not reduce_topk:
+            c3_off = off["c3"] - base
+            return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
+        check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
+        return out
     check(lib.chitu_hip_moe_gemm_bf16(ptr(hidden_states), i32(topk), ptr(w1), ptr(w1_scale), kind, sorted_p, experts_ptr,
                                       npost_p, ptr(None), i32(0), i32(0), i32(1), P("h"), i64(numel), i64(I), i64(K),
                                       i64(max_mblocks), st), "moe gemm1 (bf16 activations, silu fused)")
