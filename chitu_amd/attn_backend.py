@@ -477,9 +477,10 @@ class HipAttnBackend(AttnBackend):
 
     def _gqa_varlen_causal(self, q, k, v, cu_seqlens, max_seqlen, softmax_scale, window_left=-1, softcap=0.0):
         """Causal GQA / MHA prefill attention (Attention.prefill_forward, models/model.py:104-132), head_dim 128:
-        q [T, Hq, 128], k / v [T, Hkv, 128].  Default: the flash kernel chitu_hip_gqa_prefill.  CHITU_GQA_PREFILL=compose
-        (and shapes the kernel does not take): the round-2 composition from the decode kernel -- keys / values staged once
-        into 256-token pages, every query token one decode "sequence" of length pos + 1 over its own sequence's pages
+        q [T, Hq, 128], k / v [T, Hkv, 128].  Default: the flash kernel, chitu_hip_gqa_prefill at a group size G = Hq / Hkv that
+        is a power of two and chitu_ext4_gqa_prefill (the same kernel, include/chitu_hip_ext4.h) at every other G <= 32.
+        CHITU_GQA_PREFILL=compose (and shapes the kernel does not take; the decode kernel stops at G = 16): the round-2
+        composition from the decode kernel -- keys / values staged once into 256-token pages, every query token one decode "sequence" of length pos + 1 over its own sequence's pages
         (chitu_hip_gqa_decode): exact causal attention with the decode numerics, KV re-read once per query token; kept
         as the cross-check.  window_left >= 0 (a token sees itself and the window_left before it) or softcap > 0:
         chitu_hip_gqa_prefill_window; the composition passes both on to the windowed decode launch.  No host sync either way."""
@@ -489,8 +490,7 @@ class HipAttnBackend(AttnBackend):
             return q.new_empty(0, Hq, D)
         dev = q.device
         G = Hq // Hkv
-        if (os.environ.get("CHITU_GQA_PREFILL", "flash") != "compose" and D == 128 and Hq % Hkv == 0 and G <= 32
-                and (G & (G - 1)) == 0):
+        if os.environ.get("CHITU_GQA_PREFILL", "flash") != "compose" and D == 128 and Hq % Hkv == 0 and G <= 32:
             # chitu_hip_gqa_prefill (csrc/gqa_prefill_flash.hip): 128 Q rows (128 / G tokens x G heads of one KV head) per
             # workgroup against 64-key K / V tiles; KV read once per 128 / G query tokens instead of once per token
             def ok(t):
@@ -504,7 +504,9 @@ class HipAttnBackend(AttnBackend):
             args = (ptr(qq), i64(qq.stride(0)), i64(qq.stride(1)), ptr(kk), i64(kk.stride(0)), i64(kk.stride(1)), ptr(vv),
                     i64(vv.stride(0)), i64(vv.stride(1)), ptr(cu32), i32(cu32.numel() - 1), i32(int(max_seqlen)), f32(softmax_scale),
                     ptr(out), i32(Hq), i32(Hkv), i32(D))
-            if window_left >= 0 or softcap > 0.0:
+            if (G & (G - 1)) != 0:
+                check(_lib.lib().chitu_ext4_gqa_prefill(*args, i32(window_left), f32(softcap), stream_ptr()), "ext4_gqa_prefill")
+            elif window_left >= 0 or softcap > 0.0:
                 check(_lib.lib().chitu_hip_gqa_prefill_window(*args, i32(window_left), f32(softcap), stream_ptr()), "gqa_prefill_window")
             else:
                 check(_lib.lib().chitu_hip_gqa_prefill(*args, stream_ptr()), "gqa_prefill")
@@ -590,9 +592,9 @@ class HipAttnBackend(AttnBackend):
         of a sequence, the new rows included; block_table [n_seq, max_pages] int32; max_seqlen_q bounds the launch.  Query i of
         sequence s sits at position cache_seqlens[s] - n_s + i and sees the keys up to itself (the causal mask aligned to the bottom
         right), within window_size = (W, 0) the last W + 1 of them; softcap as in attn_with_kvcache.  Returns [T, Hq, 128].
-        One launch of chitu_hip_gqa_prefill_paged (csrc/gqa_prefill_flash.hip, kPaged): the pages are read once per 128 / (Hq / Hkv)
-        query tokens.  An fp8 cache raises NotImplementedError (the LDS-DMA cannot widen 144-byte rows), as does a mask that is
-        not causal."""
+        One launch of chitu_hip_gqa_prefill_paged (csrc/gqa_prefill_flash.hip, kPaged; chitu_ext4_gqa_prefill_paged when
+        G = Hq / Hkv is no power of two, any G <= 32): the pages are read once per 128 / G query tokens.  An fp8 cache raises
+        NotImplementedError (the LDS-DMA cannot widen 144-byte rows), as does a mask that is not causal."""
         if is_fp8_gqa_cache(k_cache) or is_fp8_gqa_cache(v_cache):
             raise NotImplementedError("attn_varlen_with_kvcache reads bf16 K / V pages; the fp8 K / V cache is not implemented")
         window_left, softcap = window_and_cap(window_size, softcap, causal)
@@ -616,8 +618,10 @@ class HipAttnBackend(AttnBackend):
             q = q.contiguous()
         cu32 = cu_seqlens_q.to(device=q.device, dtype=torch.int32).contiguous()
         out = torch.empty(T, Hq, D, dtype=torch.bfloat16, device=q.device)
+        G = Hq // max(Hkv, 1)
+        entry = _lib.lib().chitu_hip_gqa_prefill_paged if (G & (G - 1)) == 0 else _lib.lib().chitu_ext4_gqa_prefill_paged
         check(
-            _lib.lib().chitu_hip_gqa_prefill_paged(
+            entry(
                 ptr(q), i64(q.stride(0)), i64(q.stride(1)), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
                 i32(Hkv), ptr(block_table), i32(block_table.stride(0)), ptr(cu32), ptr(cache_seqlens), i32(n_seq),
                 i32(int(max_seqlen_q)), f32(softmax_scale), ptr(out), i32(Hq), i32(D), i32(window_left), f32(softcap), stream_ptr(),

@@ -5,7 +5,7 @@
 //   out[t,h,:] = softmax_{s <= t, same sequence}( scale * q[t,h,:] . k[s,h / G,:] ) . v[s,h / G,:]        G = Hq / Hkv
 //
 // The structure of mla_prefill_flash.hip at head_dim 128: the G query heads of a KV head are rows of one Q matrix, a
-// workgroup owns 128 Q rows (128 / G consecutive tokens x G heads) of one KV head, each of its 4 waves 32 of them;
+// workgroup owns 128 Q rows (128 / G consecutive tokens x G heads; any G <= 32, see kEven) of one KV head, each of its 4 waves 32;
 //   * Q fragments in registers (8 x 4 VGPRs), S^T = K Q^T by v_mfma_f32_32x32x16_bf16 so a Q row's scores of a 32-key block
 //     sit in one lane pair: in-lane softmax, running maximum moved only when a block outgrows it by 2^8 (deferred rescale);
 //   * O^T = V^T P^T: bf16 P is already the B fragment, V^T fragments by ds_read_b64_tr_b16, the 32 x 128 accumulator (64
@@ -31,7 +31,7 @@
 // it) included; P = L - n is the prefix.  Three things change and nothing else:
 //   * positions: blocks of BQ query tokens start at the first NEW token (p0 is local to them; Q rows and output rows are
 //     cu_seqlens[s] + local), every position compared against a key is P + local; 64-key tiles still start at key 0.  At P = 0 this
-//     is the contiguous kernel block for block, at P % 128 == 0 it is the contiguous kernel's blocks P / BQ ..: bit-identical
+//     is the contiguous kernel block for block, at P % 128 == 0 (P % BQ == 0) it is the contiguous kernel's blocks P / BQ ..: bit-identical
 //     outputs (the wave-wide rescale vote sees the same rows).  A query at a negative position (L < n) stores zeros.
 //   * issue(): key position t lives at cache row table[s][t / page_size] * page_size + t % page_size.  Positions are clamped to
 //     [lo, L - 1] first (lo: the block's lowest visible key, 0 without a window), so no byte of a row >= L or before the window
@@ -47,6 +47,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "chitu_hip_ext4.h"
 #include "lds_dma.h"
 
 namespace chitu {
@@ -63,7 +64,9 @@ constexpr float kDefer = 8.0f;
 typedef float f32x16g __attribute__((ext_vector_type(16)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4_gp;
 
-template <int G, bool kWin = false, bool kPaged = false>  // G: query heads per KV head (1 .. 32, a power of two)
+// GT: query heads per KV head, 1 .. 32; 0: taken at run time from the launch (Hq / gridDim.z).  G is used in the set-up and the
+// epilogue only, never in the tile loop.
+template <int GT, bool kWin = false, bool kPaged = false>
 __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
     const bf16_t* __restrict__ q, int64_t q_st, int64_t q_sh, const bf16_t* __restrict__ k, int64_t k_st, int64_t k_sh,
     const bf16_t* __restrict__ v, int64_t v_st, int64_t v_sh, const int32_t* __restrict__ cu_seqlens, float scale,
@@ -71,8 +74,14 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
     const int32_t* __restrict__ block_table, int table_stride, int page_size) {
     // kPaged: k / v are the caches, k_st / v_st = kv_heads * 128, k_sh / v_sh = 128, cu_seqlens = cu_seqlens_q
     using namespace gpf;
-    constexpr int TPW = 32 / G;   // query tokens per wave
-    constexpr int BQ = 4 * TPW;   // per workgroup
+    // kEven (G divides 32): a wave holds 32 / G whole tokens and all 128 rows are live.  Otherwise Q row R = 32 wave + row is
+    // head R % G of token R / G -- a token's heads may lie in two waves, which nothing minds: a row is one MFMA column with its
+    // own in-lane softmax -- and the 128 - BQ * G rows after the last live one duplicate it (the same position: the same mask,
+    // the same vote in the rescale ballot, a finite running maximum) and store nothing.
+    constexpr bool kEven = GT > 0 && 32 % GT == 0;
+    constexpr int GE = kEven ? GT : 1;  // (the divisor of the kEven arms below, so that they compile at GT = 0)
+    const int G = GT > 0 ? GT : Hq / (int)gridDim.z;
+    const int BQ = 128 / G;  // query tokens per workgroup
     __shared__ __attribute__((aligned(16))) uint8_t smem[2 * kBuf];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -85,11 +94,16 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
     if (p0 >= n) return;
     const int nq = min(BQ, n - p0);
     const int n_keys = P + p0 + nq;
-    const int tq = wave * TPW + row / G;    // this lane's query token within the block (one past the end repeats the last, stores nothing)
+    const int R = kEven ? 0 : min(wave * 32 + row, BQ * G - 1);     // !kEven: this lane's Q row, a padding row taking the last live one
+    auto live = [&] { return kEven || wave * 32 + row < BQ * G; };  // not a padding row
+    // this lane's head within the group and its query token within the block (one past the end repeats the last, stores nothing).
+    // The kEven arms divide unsigned, which is what keeps those kernels' code what it was before GT = 0 and !kEven existed.
+    auto hq = [&] { return kEven ? (int)((unsigned)row % (unsigned)GE) : R % G; };
+    const int tq = kEven ? wave * (32 / GE) + (int)((unsigned)row / (unsigned)GE) : R / G;
     const int tl = p0 + min(tq, nq - 1);    // its index among the sequence's query tokens
     if (kPaged && n_keys <= 0) {            // every query of the block sits before key 0 (L < n): zeros, no key is touched
-        if (tq < nq && kvh * G + row % G < Hq) {
-            bf16_t* dst = out + ((int64_t)(s0 + p0 + tq) * Hq + kvh * G + row % G) * kD + 64 * hi;
+        if (live() && tq < nq && kvh * G + hq() < Hq) {
+            bf16_t* dst = out + ((int64_t)(s0 + p0 + tq) * Hq + kvh * G + hq()) * kD + 64 * hi;
             for (int i = 0; i < 8; ++i) *reinterpret_cast<i32x4*>(dst + 8 * i) = i32x4{0, 0, 0, 0};
         }
         return;
@@ -101,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
     // its position: keys 0 .. pq (kWin: klo .. pq).  kPaged: a row before key 0 computes as position 0 and stores zeros
     const int pq = kPaged ? max(P + tl, 0) : tl;
     const int klo = win ? pq - window_left : 0;
-    const int head = kvh * G + row % G;
+    const int head = kvh * G + hq();
     const bf16_t* kbase = k + (kPaged ? 0 : (int64_t)s0 * k_st) + (int64_t)kvh * k_sh;  // kPaged: cache rows, not rows of this call
     const bf16_t* vbase = v + (kPaged ? 0 : (int64_t)s0 * v_st) + (int64_t)kvh * v_sh;
     const uint32_t lds0 = lds_offset_of(&smem[0]);
@@ -263,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
 
     // ---- epilogue: lane holds dims 32 cb + 8 rq + 4 hi + {0..3} of its row: 8-byte stores (l and l ^ 32 fill 16 bytes)
     const float inv = kPaged && P + tl < 0 ? 0.f : 1.0f / (l + __shfl_xor(l, 32, 64));
-    if (tq >= nq || head >= Hq) return;
+    if (!live() || tq >= nq || head >= Hq) return;
     bf16_t* dst = out + ((int64_t)(s0 + p0 + tq) * Hq + head) * kD + 4 * hi;
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb) {
@@ -281,18 +295,19 @@ __global__ __launch_bounds__(256, 2) void gqa_prefill_flash_kernel(
 
 namespace chitu {
 
-// window_left = -1 and softcap = 0 (chitu_hip_gqa_prefill): the kernels without the window / cap code
+// window_left = -1 and softcap = 0 (chitu_hip_gqa_prefill): the kernels without the window / cap code.  any_group
+// (chitu_hip_ext4.h): every G <= 32 instead of the powers of two; at a power of two the launch is the same either way.
 static int gqa_prefill_launch(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16, int64_t k_stride_t,
                               int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t, int64_t v_stride_h,
                               const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen, float softmax_scale, void* out_bf16,
                               int32_t q_heads, int32_t kv_heads, int32_t head_dim, int32_t window_left, float softcap,
-                              void* stream) {
+                              void* stream, bool any_group = false) {
     CHITU_REQUIRE(q_bf16 && k_bf16 && v_bf16 && cu_seqlens && out_bf16 && n_seq >= 0 && max_seqlen >= 0);
     CHITU_REQUIRE(q_heads >= 1 && kv_heads >= 1 && q_heads % kv_heads == 0);
     CHITU_REQUIRE(window_left >= -1 && softcap >= 0.f);  // (a NaN cap fails the comparison)
     if (head_dim != gpf::kD) return CHITU_ERR_UNSUPPORTED;
     const int G = q_heads / kv_heads;
-    if (G > 32 || (G & (G - 1)) != 0) return CHITU_ERR_UNSUPPORTED;
+    if (G > 32 || (!any_group && (G & (G - 1)) != 0)) return CHITU_ERR_UNSUPPORTED;
     CHITU_REQUIRE((q_stride_t | q_stride_h | k_stride_t | k_stride_h | v_stride_t | v_stride_h) % 8 == 0);
     CHITU_REQUIRE(((uintptr_t)q_bf16 | (uintptr_t)k_bf16 | (uintptr_t)v_bf16 | (uintptr_t)out_bf16) % 16 == 0);
     if (n_seq == 0 || max_seqlen == 0) return CHITU_OK;
@@ -314,7 +329,13 @@ static int gqa_prefill_launch(const void* q_bf16, int64_t q_stride_t, int64_t q_
         case 4: LAUNCH_G(4); break;
         case 8: LAUNCH_G(8); break;
         case 16: LAUNCH_G(16); break;
-        default: LAUNCH_G(32); break;
+        case 32: LAUNCH_G(32); break;
+        case 3: LAUNCH_G(3); break;   // the group sizes of published models that do not divide 32 ...
+        case 5: LAUNCH_G(5); break;
+        case 6: LAUNCH_G(6); break;
+        case 7: LAUNCH_G(7); break;
+        case 12: LAUNCH_G(12); break;
+        default: LAUNCH_G(0); break;  // ... and every other one: G at run time
     }
 #undef LAUNCH_G
 #undef LAUNCH_GW
@@ -327,14 +348,14 @@ static int gqa_prefill_paged_launch(const void* q_bf16, int64_t q_stride_t, int6
                                     const int32_t* block_table, int32_t table_stride, const int32_t* cu_seqlens_q,
                                     const int32_t* seqlens_k, int32_t n_seq, int32_t max_seqlen_q, float softmax_scale,
                                     void* out_bf16, int32_t q_heads, int32_t head_dim, int32_t window_left, float softcap,
-                                    void* stream) {
+                                    void* stream, bool any_group = false) {
     CHITU_REQUIRE(q_bf16 && k_cache && v_cache && block_table && cu_seqlens_q && seqlens_k && out_bf16);
     CHITU_REQUIRE(n_seq >= 0 && max_seqlen_q >= 0 && num_pages >= 1 && table_stride >= 1);
     CHITU_REQUIRE(q_heads >= 1 && kv_heads >= 1 && q_heads % kv_heads == 0);
     CHITU_REQUIRE(window_left >= -1 && softcap >= 0.f);  // (a NaN cap fails the comparison)
     if (head_dim != gpf::kD) return CHITU_ERR_UNSUPPORTED;
     const int G = q_heads / kv_heads;
-    if (G > 32 || (G & (G - 1)) != 0) return CHITU_ERR_UNSUPPORTED;
+    if (G > 32 || (!any_group && (G & (G - 1)) != 0)) return CHITU_ERR_UNSUPPORTED;
     if (page_size < 16 || page_size % 16 != 0) return CHITU_ERR_UNSUPPORTED;
     CHITU_REQUIRE((q_stride_t | q_stride_h) % 8 == 0);
     CHITU_REQUIRE(((uintptr_t)q_bf16 | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out_bf16) % 16 == 0);
@@ -358,7 +379,13 @@ static int gqa_prefill_paged_launch(const void* q_bf16, int64_t q_stride_t, int6
         case 4: LAUNCH_G(4); break;
         case 8: LAUNCH_G(8); break;
         case 16: LAUNCH_G(16); break;
-        default: LAUNCH_G(32); break;
+        case 32: LAUNCH_G(32); break;
+        case 3: LAUNCH_G(3); break;   // the group sizes of published models that do not divide 32 ...
+        case 5: LAUNCH_G(5); break;
+        case 6: LAUNCH_G(6); break;
+        case 7: LAUNCH_G(7); break;
+        case 12: LAUNCH_G(12); break;
+        default: LAUNCH_G(0); break;  // ... and every other one: G at run time
     }
 #undef LAUNCH_G
 #undef LAUNCH_GW
@@ -396,4 +423,26 @@ extern "C" int chitu_hip_gqa_prefill_window(const void* q_bf16, int64_t q_stride
     return chitu::gqa_prefill_launch(q_bf16, q_stride_t, q_stride_h, k_bf16, k_stride_t, k_stride_h, v_bf16, v_stride_t, v_stride_h,
                                      cu_seqlens, n_seq, max_seqlen, softmax_scale, out_bf16, q_heads, kv_heads, head_dim, window_left,
                                      softcap, stream);
+}
+
+// ---- chitu_hip_ext4.h: the same launchers at any group size
+extern "C" int chitu_ext4_gqa_prefill(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_bf16,
+                                      int64_t k_stride_t, int64_t k_stride_h, const void* v_bf16, int64_t v_stride_t,
+                                      int64_t v_stride_h, const int32_t* cu_seqlens, int32_t n_seq, int32_t max_seqlen,
+                                      float softmax_scale, void* out_bf16, int32_t q_heads, int32_t kv_heads, int32_t head_dim,
+                                      int32_t window_left, float softcap, void* stream) {
+    return chitu::gqa_prefill_launch(q_bf16, q_stride_t, q_stride_h, k_bf16, k_stride_t, k_stride_h, v_bf16, v_stride_t, v_stride_h,
+                                     cu_seqlens, n_seq, max_seqlen, softmax_scale, out_bf16, q_heads, kv_heads, head_dim, window_left,
+                                     softcap, stream, true);
+}
+
+extern "C" int chitu_ext4_gqa_prefill_paged(const void* q_bf16, int64_t q_stride_t, int64_t q_stride_h, const void* k_cache,
+                                            const void* v_cache, int64_t num_pages, int32_t page_size, int32_t kv_heads,
+                                            const int32_t* block_table, int32_t table_stride, const int32_t* cu_seqlens_q,
+                                            const int32_t* seqlens_k, int32_t n_seq, int32_t max_seqlen_q, float softmax_scale,
+                                            void* out_bf16, int32_t q_heads, int32_t head_dim, int32_t window_left, float softcap,
+                                            void* stream) {
+    return chitu::gqa_prefill_paged_launch(q_bf16, q_stride_t, q_stride_h, k_cache, v_cache, num_pages, page_size, kv_heads,
+                                           block_table, table_stride, cu_seqlens_q, seqlens_k, n_seq, max_seqlen_q, softmax_scale,
+                                           out_bf16, q_heads, head_dim, window_left, softcap, stream, true);
 }

@@ -1,4 +1,4 @@
-"""Qwen3 dense models (0.6B, 1.7B, 4B, 8B, 32B) on the Llama-family decode path.
+"""Qwen3 dense models (0.6B, 1.7B, 4B, 8B, 14B, 32B) on the Llama-family decode path.
 
 Against a Llama block a Qwen3 block differs in three things, none of which the reference has (it has no Qwen3 model):
   * an RMSNorm with a learned [head_dim] weight on every q head and every k head, after the projection and before RoPE --
@@ -7,9 +7,9 @@ Against a Llama block a Qwen3 block differs in three things, none of which the r
   * head_dim is a field of the config, not dim // n_heads (Qwen3-4B: dim 2560, 32 heads of 128);
   * the small sizes tie the output head to the embedding (tie_word_embeddings: checkpoint.load_checkpoint_hf_llama fills
     the head from the embedding; the decoder keeps two parameters).
-RoPE is half split ("hf-llama"), there is no qkv bias, and G = n_heads / n_kv_heads is a power of two for every size but
-14B (G = 5, which the prefill kernels refuse).  Everything else -- prefill, prefill_continue, decode, decode_multi, generate*,
-kv_cache_dtype="fp8", sliding_window, hipGraph capture -- is LlamaDecoder's.
+RoPE is half split ("hf-llama") and there is no qkv bias.  G = n_heads / n_kv_heads is 2, 2, 4, 4, 5, 8: the attention
+kernels take every G (prefill at a G that is no power of two through include/chitu_hip_ext4.h).  Everything else -- prefill,
+prefill_continue, decode, decode_multi, generate*, kv_cache_dtype="fp8", sliding_window, hipGraph capture -- is LlamaDecoder's.
 """
 
 from dataclasses import dataclass

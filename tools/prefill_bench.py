@@ -4,12 +4,17 @@ One prompt of T tokens through `DeepSeekV3Decoder.prefill` (eager launches: abso
 that stream the weights once per 64 rows, fused MoE over T * 8 slots), T in {128, 512, 2048}; ms per layer and the
 rank's tokens/s extrapolated to 61 layers.  Decode is the metric; this records where the step before it stands.
 
-python tools/prefill_bench.py --paged-gqa [--layers 4] [--kernel-only] [--out FILE]: what the block table costs the GQA flash prefill, and what
+python tools/prefill_bench.py --paged-gqa [--heads HQ,HKV] [--layers 4] [--kernel-only] [--out FILE]: what the block table costs the GQA flash prefill, and what
 continued prefill buys.  (1) Llama-3-8B heads (32 q / 8 kv), prefix 0, n = 2048 and 8192 new tokens, pages of 16 and
 512 tokens in a shuffled pool: chitu_hip_gqa_prefill on the contiguous rows against chitu_hip_gqa_prefill_paged over the pages, in
 ONE process, launches alternated after warm-up, 5 back-to-back launches per timed interval; the outputs are checked bit-identical
 first.  (2) A Llama-3-8B-shaped stack of --layers layers with a 2048-token prefix cached: prefill_continue of 512 tokens against the
 same 512 tokens as 64 decode_multi steps of 8 (graph replay), alternated, the cache rolled back in between.  Median [min .. max].
+--heads HQ,HKV (default 32,8): the same at another head count, the stack's hidden size being 128 HQ (40,8 is Qwen3-14B,
+24,8 Llama-3.2-3B, 28,4 Qwen2.5-7B).  At a group size that is no power of two the launches are chitu_ext4_gqa_prefill[_paged], and
+part (1) has a third arm, the composition from the decode kernel (CHITU_GQA_PREFILL=compose: what ran for such a shape before
+those entries existed; its output is checked against the flash kernel's at 1e-2 of the peak first).  ns_per_q_row: the flash
+launch's median over the n * HQ live Q rows, the figure to compare across group sizes.
 
 python tools/prefill_bench.py --paged-mla [--layers 4] [--kv bf16|fp8] [--kernel-only] [--flash-only] [--out FILE]: the same two
 questions for DeepSeek-V3's continued prefill over the latent cache.  (1) 16 heads, (P, n) = (2048, 512), pages of 64
@@ -103,6 +108,7 @@ def paged_gqa_main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--paged-gqa", action="store_true")
     ap.add_argument("--layers", type=int, default=4)
+    ap.add_argument("--heads", default="32,8", help="HQ,HKV")
     ap.add_argument("--repeats", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--kernel-only", action="store_true", help="part (1) only")
@@ -110,7 +116,9 @@ def paged_gqa_main():
     a = ap.parse_args()
     rows = [{"box": _box(), "device": torch.cuda.get_device_name(0)}]
     print(json.dumps(rows[0]), flush=True)
-    Hq, Hkv = 32, 8
+    Hq, Hkv = (int(x) for x in a.heads.split(","))
+    G = Hq // Hkv
+    with_compose = (G & (G - 1)) != 0 and G <= 16  # (the decode kernel, which the composition runs, stops at G = 16)
     be = HipAttnBackend(local_n_heads=Hq, max_seq_len=8192)
     g = torch.Generator(device="cuda").manual_seed(0)
     for n in (2048, 8192):
@@ -132,15 +140,36 @@ def paged_gqa_main():
                 rows.append({"n": n, "page": page, "error": "outputs differ: no times"})
                 print(json.dumps(rows[-1]), flush=True)
                 continue
+            if with_compose and page == 16:  # (the composition stages its own pages: one page size is enough)
+                def compose():
+                    os.environ["CHITU_GQA_PREFILL"] = "compose"
+                    try:
+                        return be.attn_varlen_func(q, k, v, cu, cu, n, n, causal=True)
+                    finally:
+                        del os.environ["CHITU_GQA_PREFILL"]
+
+                want = arms["contiguous"]().float()
+                err = float((compose().float() - want).abs().max() / want.abs().max())
+                if not err < 1e-2:
+                    rows.append({"n": n, "page": page, "error": f"composition and flash kernel differ by {err:.3e} of the peak: no times"})
+                    print(json.dumps(rows[-1]), flush=True)
+                    continue
+                arms["compose"] = compose
             t = {k_: _stats(v_) for k_, v_ in _alternate(arms, a.warmup, a.repeats, 5).items()}
             rows.append({"what": "kernel", "Hq": Hq, "Hkv": Hkv, "prefix": 0, "n": n, "page": page, **t,
-                         "paged_over_contiguous": round(t["paged"]["median_us"] / t["contiguous"]["median_us"], 4)})
+                         "paged_over_contiguous": round(t["paged"]["median_us"] / t["contiguous"]["median_us"], 4),
+                         "ns_per_q_row": round(t["contiguous"]["median_us"] * 1e3 / (n * Hq), 4)})
+            if "compose" in t:
+                rows[-1]["compose_over_flash"] = round(t["compose"]["median_us"] / t["contiguous"]["median_us"], 3)
             print(json.dumps(rows[-1]), flush=True)
             del kc, vc
     if a.kernel_only:
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(rows, f, indent=1)
         return
     # (2) the model path: 512 tokens onto a cached 2048-token prefix
-    args = LlamaArgs(n_layers=a.layers)
+    args = LlamaArgs(n_layers=a.layers, n_heads=Hq, n_kv_heads=Hkv, dim=128 * Hq)
     cache = PagedKVCacheManager(0, a.layers, num_hot_req=1, block_size=256, max_seq_len=4096, device="cuda",
                                 n_local_kv_heads=args.n_kv_heads, head_dim=128, dtype=torch.bfloat16)
     model = LlamaDecoder(args, cache, HipAttnBackend(local_n_heads=args.n_heads, max_seq_len=4096), max_position_embeddings=4096, device="cuda")
@@ -163,7 +192,7 @@ def paged_gqa_main():
         cache.rollback(["r"], [512])
 
     t = {k_: _stats(v_) for k_, v_ in _alternate({"prefill_continue_512": continued, "decode_multi_64x8": multi_steps}, 2, 7, 1).items()}
-    rows.append({"what": "model", "layers": a.layers, "prefix": 2048, "new_tokens": 512, **t,
+    rows.append({"what": "model", "Hq": Hq, "Hkv": Hkv, "layers": a.layers, "prefix": 2048, "new_tokens": 512, **t,
                  "continue_over_multi": round(t["prefill_continue_512"]["median_us"] / t["decode_multi_64x8"]["median_us"], 4)})
     print(json.dumps(rows[-1]), flush=True)
     if a.out:
