@@ -468,7 +468,8 @@ def preprocess_hf_llama(state: Mapping[str, torch.Tensor], n_heads: int, n_kv_he
 
 _LLAMA_MODULE_NAMES = (("embed_tokens.weight", "embed_weight"), ("lm_head.weight", "head_weight"), ("norm.weight", "norm"),
                        (".input_layernorm.weight", ".attn_norm"), (".post_attention_layernorm.weight", ".ffn_norm"),
-                       (".self_attn.qkv_proj.weight", ".attn.wqkv"), (".self_attn.o_proj.weight", ".attn.wo"),
+                       (".self_attn.qkv_proj.weight", ".attn.wqkv"), (".self_attn.qkv_proj.bias", ".attn.bqkv"),
+                       (".self_attn.o_proj.weight", ".attn.wo"),
                        (".self_attn.q_norm.weight", ".attn.q_norm"), (".self_attn.k_norm.weight", ".attn.k_norm"),
                        (".mlp.gate_up_proj.weight", ".ffn.w13"), (".mlp.down_proj.weight", ".ffn.w2"), (".mlp.gate.weight", ".ffn.gate"))
 
@@ -480,10 +481,15 @@ def _rename_llama(name: str) -> str:
     return name
 
 
-def to_llama_module_names(state: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """Reference names -> chitu_amd.llama.LlamaDecoder's parameters.  Biases (Qwen-style qkv bias) have no parameter there
-    and are refused rather than dropped."""
-    bias = [k for k in state if k.endswith(".bias")]
+_QKV_BIAS = re.compile(r"(?:.*\.)?layers\.\d+\.self_attn\.qkv_proj\.bias$")
+
+
+def to_llama_module_names(state: Mapping[str, torch.Tensor], qkv_bias: bool = False) -> Dict[str, torch.Tensor]:
+    """Reference names -> chitu_amd.llama.LlamaDecoder's parameters.  A bias has a parameter there only as the merged q / k / v
+    bias of a model built with qkv_bias (Qwen2: LlamaAttention.bqkv): with qkv_bias=True exactly the per-layer
+    `self_attn.qkv_proj.bias` is accepted and renamed `.attn.bqkv`.  Every other bias -- and, with the default, every bias --
+    is refused rather than dropped."""
+    bias = [k for k in state if k.endswith(".bias") and not (qkv_bias and _QKV_BIAS.match(k))]
     if bias:
         raise NotImplementedError(f"LlamaDecoder has no bias parameters: {bias[:4]}")
     return {_rename_llama(k): v for k, v in state.items()}
@@ -539,7 +545,7 @@ def load_checkpoint_hf_llama(model, path: str, rank: int = 0, world: int = 1, sk
         state["lm_head.weight"] = state["model.embed_tokens.weight" if "model.embed_tokens.weight" in state else "embed_tokens.weight"]
     st = preprocess_hf_llama(state, args.n_heads, args.n_kv_heads, args.dim, rank, world, mixtral=mixtral,
                              router_row_parallel=False, head_dim=args.head_dim)
-    st = to_mixtral_module_names(st, args.num_local_experts) if mixtral else to_llama_module_names(st)
+    st = to_mixtral_module_names(st, args.num_local_experts) if mixtral else to_llama_module_names(st, qkv_bias=getattr(args, "qkv_bias", False))
     load_deepseek_v3(model, st)  # the generic strict, shape- and dtype-checked in-place copy
 
 

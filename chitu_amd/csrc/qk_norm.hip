@@ -11,30 +11,10 @@
 // The lane mapping is gqa_kv_fp8.hip's: one 16-lane DPP row per head, 8 channels per lane, the sum of squares as four row
 // rotations on the VALU; a wave takes four heads.  With the half-split layout lane l's rotation partner is lane (l ^ 8)'s
 // normalised chunk, fetched by one more row rotation (row_ror:8) per channel instead of a second load and a second norm.
-#include "gqa_kv_fp8.h"
+#include "head_rope.h"
 #include "chitu_hip_ext.h"
 
 namespace chitu {
-
-// The cos / sin values of one lane's channels.  layout 0: lane l owns the pairs 4 l .. 4 l + 3 (c[0..3]); layout 1: its
-// channels 8 l + k rotate by entry 8 (l & 7) + k (c[0..7]).
-struct QkRot {
-    float c[8], s[8];
-};
-
-__device__ __forceinline__ QkRot qk_load_rot(int l, const float* __restrict__ cb, const float* __restrict__ sb, int layout) {
-    QkRot t;
-    const int at = layout == 0 ? 4 * l : 8 * (l & 7);
-    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cb + at), s0 = *reinterpret_cast<const f32x4*>(sb + at);
-    f32x4 c1 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
-    if (layout != 0) {
-        c1 = *reinterpret_cast<const f32x4*>(cb + at + 4);
-        s1 = *reinterpret_cast<const f32x4*>(sb + at + 4);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) t.c[k] = c0[k], t.s[k] = s0[k], t.c[4 + k] = c1[k], t.s[4 + k] = s1[k];
-    return t;
-}
 
 // One head = one 16-lane DPP row, all 16 lanes active: lane l holds channels 8 l .. 8 l + 7 (xraw) and their weights (wraw).
 // Returns the lane's 8 normalised and rotated channels as bf16 bits.
@@ -50,23 +30,7 @@ __device__ __forceinline__ i32x4 qk_norm_rope_head(int l, const i32x4 xraw, cons
     const float rr = rsqrtf(ss / 128.0f + eps);
 #pragma unroll
     for (int k = 0; k < 8; ++k) n[k] = round_bf16((x[k] * rr) * w[k]);
-    i32x4 o;
-    if (layout == 0) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            o[k] = (int)f32x2_to_bf16x2(n[2 * k] * t.c[k] - n[2 * k + 1] * t.s[k], n[2 * k + 1] * t.c[k] + n[2 * k] * t.s[k]);
-    } else {
-        float r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            const float y = dpp_row<0x128>(n[k]);  // row_ror:8 = lane l ^ 8
-            // l < 8: n is x0 (channel i), y is x1 (channel i + 64); else the other way round
-            r[k] = l < 8 ? n[k] * t.c[k] - y * t.s[k] : n[k] * t.c[k] + y * t.s[k];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) o[k] = (int)f32x2_to_bf16x2(r[2 * k], r[2 * k + 1]);
-    }
-    return o;
+    return rope_head_row16(l, n, t, layout);
 }
 
 // gqa_qkv_post_kernel (kv.hip) / gqa_qkv_post_kv_fp8_kernel (gqa_kv_fp8.hip) with the head norm in front of the rotation.

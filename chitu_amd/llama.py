@@ -102,6 +102,16 @@ class LlamaAttention(torch.nn.Module):
             self.q_norm = _param(self.hd, device=device)
             self.k_norm = _param(self.hd, device=device)
             self.qk_eps = args.norm_eps
+        # Qwen2: a bias on the q / k / v projections, one merged row laid out like a row of wqkv's output (ColumnParallel like
+        # wqkv: this rank's q heads, then k heads, then v heads).  It is added in the launch that rotates q and k and appends k and
+        # v (decode) or in the prompt's one rotation launch (prefill), never as a launch of its own.
+        self.qkv_bias = bool(getattr(args, "qkv_bias", False))
+        if self.qkv_bias:
+            if self.qk_norm:
+                raise ValueError("qkv_bias together with qk_norm: no launch adds a bias in front of the head norm (no published model has both)")
+            if self.hd != 128:
+                raise ValueError(f"qkv_bias: the bias launches are head_dim 128, got {self.hd} (Qwen2.5-0.5B has 64)")
+            self.bqkv = _param((self.hq + 2 * self.hkv) * self.hd, device=device)
 
     def decode_forward_paged(self, x, cos, sin, q_len=1):
         """x = attn_norm(h) bf16 [bs, dim] -> wo(attention) before the all-reduce (model.py:167-198)."""
@@ -124,6 +134,11 @@ class LlamaAttention(torch.nn.Module):
             post = ops.gqa_qkv_norm_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_norm_post
             q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), self.q_norm, self.k_norm,
                      self.qk_eps, rotary_type=self.rotary_type)
+            return self.decode_from_q(q, q_len)
+        if self.qkv_bias:  # the bias in front of the rotation, same launch
+            post = ops.gqa_qkv_bias_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_bias_post
+            q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), self.bqkv,
+                     rotary_type=self.rotary_type)
             return self.decode_from_q(q, q_len)
         post = ops.gqa_qkv_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_post
         q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), rotary_type=self.rotary_type)
@@ -151,8 +166,8 @@ class LlamaAttention(torch.nn.Module):
         """Small decode batches: residual add + attn_norm + wqkv projection [+ RoPE and the K / V page append when the
         rotary pairs are interleaved] in ONE launch.  Returns (x + pending, wo(attention) before the all-reduce).  The fused
         epilogue writes bf16 page rows: an fp8 cache takes the two-launch form of "hf-llama", and so does a model with a head norm
-        (the epilogue does not normalise)."""
-        if self.rotary_type == "llama" and not self.fp8_kv and not self.qk_norm:
+        or a qkv bias (the epilogue neither normalises nor adds one)."""
+        if self.rotary_type == "llama" and not self.fp8_kv and not self.qk_norm and not self.qkv_bias:
             k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
             x, qkv = ops.bf16_linear_add_norm_qkv_post(
                 x, pending, norm_weight, eps, self.wqkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len))
@@ -161,11 +176,17 @@ class LlamaAttention(torch.nn.Module):
         return x, self.decode_from_qkv(qkv, cos, sin, q_len)
 
     def _rotate(self, qkv, cos, sin):
-        """Prefill: RoPE (behind the head norm, when the model has one) on the q and k heads of qkv [T, hq + 2 hkv, hd]."""
+        """Prefill: qkv [T, hq + 2 hkv, hd] -> (q, k, v) with RoPE on the q and k heads (behind the head norm or the bias, when the
+        model has one) and v contiguous.  With a bias the three come out of ONE launch; otherwise the rotation and the copy of v
+        are one each."""
+        if self.qkv_bias:
+            return ops.qkv_bias_rope(qkv, self.hq, self.hkv, self.bqkv, cos, sin, rotary_type=self.rotary_type)
         q, k = qkv[:, : self.hq], qkv[:, self.hq : self.hq + self.hkv]
         if self.qk_norm:
-            return ops.qk_norm_rope(q, k, self.q_norm, self.k_norm, self.qk_eps, cos, sin, rotary_type=self.rotary_type)
-        return ops.apply_rotary_pos_emb(q, k, cos, sin, rotary_type=self.rotary_type)
+            q, k = ops.qk_norm_rope(q, k, self.q_norm, self.k_norm, self.qk_eps, cos, sin, rotary_type=self.rotary_type)
+        else:
+            q, k = ops.apply_rotary_pos_emb(q, k, cos, sin, rotary_type=self.rotary_type)
+        return q, k, qkv[:, self.hq + self.hkv :].contiguous()
 
     def prefill_forward(self, x, cos, sin, varlens):
         """models/model.py:104-132: projections on all T prompt tokens, RoPE, page writes by the cache
@@ -175,8 +196,7 @@ class LlamaAttention(torch.nn.Module):
             return self.prefill_forward_paged(x, cos, sin, varlens)
         T = x.shape[0]
         qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
-        q, k = self._rotate(qkv, cos, sin)
-        v = qkv[:, self.hq + self.hkv :].contiguous()
+        q, k, v = self._rotate(qkv, cos, sin)
         if self.fp8_kv:
             # the pages take the quantised rows (the same index_copy_ scatter, over byte rows); attention runs over the
             # unquantised ones, as the MLA prefill does
@@ -195,8 +215,7 @@ class LlamaAttention(torch.nn.Module):
         assert not self.fp8_kv, "continued prefill reads bf16 K / V pages"
         T = x.shape[0]
         qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
-        q, k = self._rotate(qkv, cos, sin)
-        v = qkv[:, self.hq + self.hkv :].contiguous()
+        q, k, v = self._rotate(qkv, cos, sin)
         self.cache.finalize_cache_bylayer_prefill_continue(k, v, self.layer_id)
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
         o = self.attn_backend.attn_varlen_with_kvcache(

@@ -677,6 +677,77 @@ def qk_norm_rope(q, k, q_norm_weight, k_norm_weight, eps, cos, sin, rotary_type=
     return out_q, out_k
 
 
+def _gqa_qkv_bias_post(entry, what, qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type):
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
+    require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
+    assert qkv.stride(2) == 1 and qkv.stride(1) == 128 and qkv.stride(0) % 8 == 0, "dense heads; only the row stride is free"
+    assert bias.dtype == torch.bfloat16 and tuple(bias.shape) == ((q_heads + 2 * kv_heads) * 128,) and bias.is_contiguous()
+    assert k_cache.shape[2] == kv_heads and page_table.dtype == torch.int32 and page_table.stride(1) == 1
+    assert cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and old_seq_lens.dtype == torch.int32
+    bs = qkv.shape[0]
+    assert cos.shape == (bs, 64) and sin.shape == (bs, 64) and page_table.shape[0] >= bs and page_table.is_contiguous()
+    assert old_seq_lens.shape[0] >= bs and old_seq_lens.is_contiguous()
+    check(
+        getattr(_lib.lib(), entry)(
+            ptr(qkv), i64(qkv.stride(0)), i32(q_heads), i32(kv_heads), i32(128), ptr(cos), ptr(sin),
+            i32(0 if rotary_type == "llama" else 1), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
+            ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), ptr(bias), stream_ptr(),
+        ),
+        what,
+    )
+    return qkv[:, :q_heads]
+
+
+def gqa_qkv_bias_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type="llama"):
+    """gqa_qkv_post with Qwen2's q / k / v projection bias in front of the rotation, one launch: bias [(q_heads + 2 kv_heads) *
+    128] bf16 is added to every row (fp32 add, one bf16 rounding: a bf16 torch.add), q and k heads are then rotated; q in place,
+    k and the biased v into the token's page row.  Bit for bit gqa_qkv_post on qkv + bias.  qkv [bs, q_heads + 2*kv_heads, 128]
+    bf16 (the row stride may be padded); returns the q view."""
+    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape and k_cache.dtype == torch.bfloat16
+    assert v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4 and k_cache.shape[3] == 128
+    return _gqa_qkv_bias_post("chitu_ext5_gqa_qkv_bias_post", "gqa_qkv_bias_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
+                              page_table, old_seq_lens, bias, rotary_type)
+
+
+def gqa_qkv_bias_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type="llama"):
+    """gqa_qkv_bias_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): the bytes of gqa_kv_quant_fp8 on the
+    rows gqa_qkv_bias_post writes.  One launch; returns the q view."""
+    _check_gqa_fp8_caches(k_cache, v_cache)
+    return _gqa_qkv_bias_post("chitu_ext5_gqa_qkv_bias_post_kv_fp8", "gqa_qkv_bias_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin,
+                              k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type)
+
+
+def qkv_bias_rope(qkv, q_heads, kv_heads, bias, cos, sin, rotary_type="hf-llama"):
+    """The prefill form of gqa_qkv_bias_post, no cache: qkv [T, q_heads + 2 kv_heads, 128] bf16 (channels dense, row and head
+    strides multiples of 8 elements) plus bias, RoPE on the q and k heads, the whole prompt in one launch.  cos / sin fp32
+    [T, 64].  Returns contiguous (out_q [T, q_heads, 128], out_k, out_v [T, kv_heads, 128]), bit-identical to what the decode
+    form produces for the same rows."""
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
+    require_cuda(qkv, bias, cos, sin)
+    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
+    assert qkv.stride(2) == 1 and qkv.stride(1) % 8 == 0 and qkv.stride(0) % 8 == 0
+    assert bias.dtype == torch.bfloat16 and tuple(bias.shape) == ((q_heads + 2 * kv_heads) * 128,) and bias.is_contiguous()
+    T = qkv.shape[0]
+    assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
+    assert cos.shape == (T, 64) and sin.shape == (T, 64)
+    out_q = torch.empty(T, q_heads, 128, dtype=qkv.dtype, device=qkv.device)
+    out_k = torch.empty(T, kv_heads, 128, dtype=qkv.dtype, device=qkv.device)
+    out_v = torch.empty(T, kv_heads, 128, dtype=qkv.dtype, device=qkv.device)
+    if T == 0:
+        return out_q, out_k, out_v
+    check(
+        _lib.lib().chitu_ext5_qkv_bias_rope(
+            ptr(qkv), i64(qkv.stride(0)), i64(qkv.stride(1)), ptr(bias), ptr(cos), ptr(sin), ptr(out_q), ptr(out_k), ptr(out_v),
+            i64(T), i32(q_heads), i32(kv_heads), i32(128), i32(0 if rotary_type == "llama" else 1), stream_ptr(),
+        ),
+        "qkv_bias_rope",
+    )
+    return out_q, out_k, out_v
+
+
 def bf16_linear_silu(x: torch.Tensor, w13: torch.Tensor) -> torch.Tensor:
     """silu(x w1^T) * (x w3^T) for w13 = [w1; w3] (bf16), one launch: == silu_and_mul(bf16_linear(x, w13))."""
     require_cuda(x, w13)
