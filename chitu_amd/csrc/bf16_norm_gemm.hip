@@ -229,7 +229,9 @@ __global__ __launch_bounds__(64 * WK) void bf16_gemm_add_norm_kernel(
     add_norm_finish<WK, MR, POUT>(regs, sum_out, sum_stride, blockIdx.x == 0 && blockIdx.y == 0, M, K, eps, ybuf, nred, &po,
                                   term2_off != 0);
     // QKV: the page row's address -- old_len arrived with the prologue's loads; its dependent table load is issued here
-    // so that the round trip runs under the K loop, not after it
+    // so that the round trip runs under the K loop, not after it.  The rule is paged_token_row's (common.h), written out:
+    // through the call the entry's `>= 0` test becomes a 64-bit compare, and this launch is held to the machine code it was
+    // measured with.
     int64_t dst_row = -1;
     if (QKV && wave == 0 && head >= qa.hq) {
         const int pidx = old_len / qa.page_size;

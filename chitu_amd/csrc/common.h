@@ -206,6 +206,24 @@ __device__ __forceinline__ float row16_reduce_sum(float v) {
     return v;
 }
 
+// THE page-row rule of every launch that writes a token into a paged cache [num_pages, page_size, ...]: the row index of
+// position L of sequence b is table[b][L / page_size] * page_size + L % page_size.  False -- a negative length, a position
+// beyond the table's width or a table entry outside [0, num_pages) -- where the caller writes nothing.  L is an argument, not
+// loaded here: the table load depends on it, and a caller places the two round trips where its other work hides them.
+// (A bool and not a -1 row: a caller's `row < 0` test would stay on the valid path as one more compare and branch.)
+__device__ __forceinline__ bool paged_token_row(int b, int L, int64_t num_pages, int page_size,
+                                                const int32_t* __restrict__ table, int pages_per_seq, int64_t& row) {
+    const int pidx = L / page_size;
+    if (L >= 0 && pidx < pages_per_seq) {
+        const int64_t page = table[(int64_t)b * pages_per_seq + pidx];
+        if (page >= 0 && page < num_pages) {
+            row = page * page_size + (L % page_size);
+            return true;
+        }
+    }
+    return false;  // out-of-table: drop instead of corrupting memory
+}
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 static inline int ceil_div_i(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }

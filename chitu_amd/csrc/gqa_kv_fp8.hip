@@ -41,18 +41,14 @@ __global__ __launch_bounds__(256) void gqa_kv_dequant_fp8_kernel(const uint8_t* 
     *reinterpret_cast<i32x4*>(dst + u * 128 + l * 8) = kv_fp8_widen8((uint32_t)codes[0], (uint32_t)codes[1], s);
 }
 
-// Byte offset of position old_lens[b] of sequence b in a [pages, page, Hkv, 144] cache, or -1: the range rules of
-// append_paged_kv_kernel (kv.hip) -- a table entry outside [0, num_pages), a negative length or a position beyond the table's
-// width writes nothing.
+// Byte offset of position old_lens[b] of sequence b in a [pages, page, Hkv, 144] cache, or -1 where paged_token_row
+// (common.h) refuses: nothing is written.
 __device__ __forceinline__ int64_t gqa_kv_fp8_token_off(int b, int64_t num_pages, int page_size, int Hkv,
                                                         const int32_t* __restrict__ table, int pages_per_seq,
                                                         const int32_t* __restrict__ old_lens) {
-    const int L = old_lens[b];
-    const int pidx = L / page_size;
-    if (L < 0 || pidx >= pages_per_seq) return -1;
-    const int64_t page = table[(int64_t)b * pages_per_seq + pidx];
-    if (page < 0 || page >= num_pages) return -1;
-    return (page * page_size + (L % page_size)) * (int64_t)Hkv * kGqaKvFp8Row;
+    int64_t trow;
+    if (!paged_token_row(b, old_lens[b], num_pages, page_size, table, pages_per_seq, trow)) return -1;
+    return trow * (int64_t)Hkv * kGqaKvFp8Row;
 }
 
 // grid (ceil(batch * Hkv / 16), 2), block 256; blockIdx.y: 0 = K, 1 = V

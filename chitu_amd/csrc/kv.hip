@@ -17,12 +17,9 @@ __global__ __launch_bounds__(128) void append_paged_kv_kernel(
     const int32_t* __restrict__ table, int pages_per_seq, const uint8_t* __restrict__ this_kv,
     const int32_t* __restrict__ old_lens) {
     const int b = blockIdx.x;
-    const int L = old_lens[b];
-    const int pidx = L / page_size;
-    if (L < 0 || pidx >= pages_per_seq) return;  // out-of-table: drop instead of corrupting memory
-    const int64_t page = table[(int64_t)b * pages_per_seq + pidx];
-    if (page < 0 || page >= num_pages) return;
-    uint8_t* dst = cache + (page * page_size + (L % page_size)) * row_bytes;
+    int64_t trow;
+    if (!paged_token_row(b, old_lens[b], num_pages, page_size, table, pages_per_seq, trow)) return;
+    uint8_t* dst = cache + trow * row_bytes;
     const uint8_t* src = this_kv + (int64_t)b * row_bytes;
     if ((row_bytes & 15) == 0) {
         for (int64_t i = threadIdx.x * 16; i < row_bytes; i += blockDim.x * 16)
@@ -99,14 +96,8 @@ __global__ __launch_bounds__(256) void mla_kv_prep_kernel(
     const float* cb = cos + (int64_t)b * 32;
     const float* sb = sin + (int64_t)b * 32;
     bf16_t* row = nullptr;
-    {
-        const int L = old_lens[b];
-        const int pidx = L / page_size;
-        if (L >= 0 && pidx < pages_per_seq) {
-            const int64_t page = table[(int64_t)b * pages_per_seq + pidx];
-            if (page >= 0 && page < num_pages) row = cache + (page * page_size + (L % page_size)) * 576;
-        }
-    }
+    int64_t trow;
+    if (paged_token_row(b, old_lens[b], num_pages, page_size, table, pages_per_seq, trow)) row = cache + trow * 576;
     if (wave == 0) {
         const i32x4 raw = *reinterpret_cast<const i32x4*>(src + lane * 8);
         float v[8], ss = 0.f;
@@ -162,15 +153,8 @@ __global__ __launch_bounds__(256) void gqa_qkv_post_kernel(
 #pragma clang fp contract(off)
     const int b = blockIdx.x, half = d >> 1;
     bf16_e* row = qkv + (int64_t)b * row_stride;
-    int64_t dst_row = -1;
-    {
-        const int L = old_lens[b];
-        const int pidx = L / page_size;
-        if (L >= 0 && pidx < pages_per_seq) {
-            const int64_t page = table[(int64_t)b * pages_per_seq + pidx];
-            if (page >= 0 && page < num_pages) dst_row = (page * page_size + (L % page_size)) * (int64_t)hkv * d;
-        }
-    }
+    int64_t dst_row = -1, trow;  // the token's row in either cache, in elements
+    if (paged_token_row(b, old_lens[b], num_pages, page_size, table, pages_per_seq, trow)) dst_row = trow * (int64_t)hkv * d;
     for (int idx = threadIdx.x; idx < (hq + hkv) * half; idx += 256) {
         const int h = idx / half, i = idx % half;
         const int i0 = layout == 0 ? 2 * i : i, i1 = layout == 0 ? 2 * i + 1 : i + half;

@@ -65,8 +65,7 @@ __global__ __launch_bounds__(256) void mla_kv_dequant_fp8_kernel(const uint8_t* 
 }
 
 // Row b of the source -> position old_lens[b] of sequence b's page.  The indexing and the out-of-range rules are
-// mla_kv_row_ptr's (mla_kv_row.h): a table entry outside [0, num_pages), a negative length or a position beyond the table's
-// width writes nothing.
+// paged_token_row's (common.h): where it refuses, nothing is written.
 __global__ __launch_bounds__(256) void mla_kv_append_fp8_kernel(const bf16_t* __restrict__ src, int64_t src_stride,
                                                                 uint8_t* __restrict__ cache, int64_t num_pages, int page_size,
                                                                 const int32_t* __restrict__ table, int pages_per_seq,
@@ -74,12 +73,9 @@ __global__ __launch_bounds__(256) void mla_kv_append_fp8_kernel(const bf16_t* __
     const int lane = threadIdx.x & 63;
     const int b = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6);
     if (b >= batch) return;
-    const int L = old_lens[b];
-    const int pidx = L / page_size;
-    if (L < 0 || pidx >= pages_per_seq) return;
-    const int64_t page = table[(int64_t)b * pages_per_seq + pidx];
-    if (page < 0 || page >= num_pages) return;
-    kv_fp8_quant_row(lane, src + (int64_t)b * src_stride, cache + (page * page_size + (L % page_size)) * (int64_t)kKvFp8Row);
+    int64_t trow;
+    if (!paged_token_row(b, old_lens[b], num_pages, page_size, table, pages_per_seq, trow)) return;
+    kv_fp8_quant_row(lane, src + (int64_t)b * src_stride, cache + trow * (int64_t)kKvFp8Row);
 }
 
 }  // namespace chitu

@@ -5,7 +5,9 @@
 
 namespace chitu {
 
-// The page row of token b's new KV entry (nullptr when its table entry is out of range: nothing is written).
+// The page row of token b's new KV entry (nullptr when its table entry is out of range: nothing is written).  The rule is
+// paged_token_row's (common.h), written out: through the call, the three launches that inline this lose a branch each, and
+// they are held to the machine code they were measured with.
 __device__ __forceinline__ bf16_t* mla_kv_row_ptr(int b, bf16_t* __restrict__ cache, int64_t num_pages, int page_size,
                                                   const int32_t* __restrict__ table, int pages_per_seq,
                                                   const int32_t* __restrict__ old_lens) {

@@ -131,17 +131,13 @@ class LlamaAttention(torch.nn.Module):
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
         # RoPE(q, k) + append of k and v to their pages: one launch (fp8 cache: with quantising stores)
         if self.qk_norm:  # the head norm in front of the rotation, same launch
-            post = ops.gqa_qkv_norm_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_norm_post
-            q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), self.q_norm, self.k_norm,
-                     self.qk_eps, rotary_type=self.rotary_type)
-            return self.decode_from_q(q, q_len)
-        if self.qkv_bias:  # the bias in front of the rotation, same launch
-            post = ops.gqa_qkv_bias_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_bias_post
-            q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), self.bqkv,
-                     rotary_type=self.rotary_type)
-            return self.decode_from_q(q, q_len)
-        post = ops.gqa_qkv_post_kv_fp8 if self.fp8_kv else ops.gqa_qkv_post
-        q = post(qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), rotary_type=self.rotary_type)
+            post, extra = "gqa_qkv_norm_post", (self.q_norm, self.k_norm, self.qk_eps)
+        elif self.qkv_bias:  # the bias in front of the rotation, same launch
+            post, extra = "gqa_qkv_bias_post", (self.bqkv,)
+        else:
+            post, extra = "gqa_qkv_post", ()
+        q = getattr(ops, post + ("_kv_fp8" if self.fp8_kv else ""))(
+            qkv, self.hq, self.hkv, cos, sin, k_cache, v_cache, *self._row_tables(q_len), *extra, rotary_type=self.rotary_type)
         return self.decode_from_q(q, q_len)
 
     def decode_from_q(self, q, q_len=1):

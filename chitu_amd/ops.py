@@ -600,23 +600,37 @@ def _check_head_norm_weights(q_norm_weight, k_norm_weight):
         assert w.dtype == torch.bfloat16 and tuple(w.shape) == (128,) and w.is_contiguous()
 
 
-def _gqa_qkv_norm_post(entry, what, qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight,
-                       k_norm_weight, eps, rotary_type):
-    require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight, k_norm_weight)
+def _check_qkv_bias(bias, heads):
+    assert bias.dtype == torch.bfloat16 and tuple(bias.shape) == (heads * 128,) and bias.is_contiguous()
+
+
+def _gqa_qkv_row16_post(prefix, what, qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, rotary_type,
+                        operands, check_operands, tail):
+    """The one body of gqa_qkv_norm_post, gqa_qkv_bias_post and their _kv_fp8 forms (csrc/qkv_post_row16.hip): entry
+    prefix + what; `operands` are the tensors the entry takes besides gqa_qkv_post's, validated by check_operands(*operands);
+    tail() gives its trailing ctypes arguments, in front of the stream, once the operands are validated.  A name ending in
+    _kv_fp8 takes the fp8 caches."""
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
+    if what.endswith("_kv_fp8"):
+        _check_gqa_fp8_caches(k_cache, v_cache)
+    else:
+        assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape
+        assert k_cache.dtype == torch.bfloat16 and v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4 and k_cache.shape[3] == 128
+    require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens, *operands)
     assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
     assert qkv.stride(2) == 1 and qkv.stride(1) == 128 and qkv.stride(0) % 8 == 0, "dense heads; only the row stride is free"
-    _check_head_norm_weights(q_norm_weight, k_norm_weight)
+    check_operands(*operands)
     assert k_cache.shape[2] == kv_heads and page_table.dtype == torch.int32 and page_table.stride(1) == 1
     assert cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and old_seq_lens.dtype == torch.int32
     bs = qkv.shape[0]
     assert cos.shape == (bs, 64) and sin.shape == (bs, 64) and page_table.shape[0] >= bs and page_table.is_contiguous()
     assert old_seq_lens.shape[0] >= bs and old_seq_lens.is_contiguous()
     check(
-        getattr(_lib.lib(), entry)(
+        getattr(_lib.lib(), prefix + what)(
             ptr(qkv), i64(qkv.stride(0)), i32(q_heads), i32(kv_heads), i32(128), ptr(cos), ptr(sin),
             i32(0 if rotary_type == "llama" else 1), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
-            ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), ptr(q_norm_weight), ptr(k_norm_weight),
-            f32(eps), stream_ptr(),
+            ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), *tail(), stream_ptr(),
         ),
         what,
     )
@@ -628,23 +642,18 @@ def gqa_qkv_norm_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_t
     """gqa_qkv_post with Qwen3's per-head RMSNorm in front of the rotation, one launch: every q head and every k head is
     normalised (weights [128] bf16, fp32 arithmetic, one bf16 rounding) and then rotated; q in place, k into the token's page
     row, v copied.  qkv [bs, q_heads + 2*kv_heads, 128] bf16 (the row stride may be padded); returns the q view."""
-    if rotary_type not in ("llama", "hf-llama"):
-        raise ValueError(f"Unknown rotary type: {rotary_type}")
-    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape and k_cache.dtype == torch.bfloat16
-    assert v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4 and k_cache.shape[3] == 128
-    return _gqa_qkv_norm_post("chitu_ext_gqa_qkv_norm_post", "gqa_qkv_norm_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
-                              page_table, old_seq_lens, q_norm_weight, k_norm_weight, eps, rotary_type)
+    return _gqa_qkv_row16_post("chitu_ext_", "gqa_qkv_norm_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table,
+                               old_seq_lens, rotary_type, (q_norm_weight, k_norm_weight), _check_head_norm_weights,
+                               lambda: (ptr(q_norm_weight), ptr(k_norm_weight), f32(eps)))
 
 
 def gqa_qkv_norm_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, q_norm_weight,
                              k_norm_weight, eps, rotary_type="llama"):
     """gqa_qkv_norm_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): the bytes of gqa_kv_quant_fp8 on the
     rows gqa_qkv_norm_post writes.  One launch; returns the q view."""
-    if rotary_type not in ("llama", "hf-llama"):
-        raise ValueError(f"Unknown rotary type: {rotary_type}")
-    _check_gqa_fp8_caches(k_cache, v_cache)
-    return _gqa_qkv_norm_post("chitu_ext_gqa_qkv_norm_post_kv_fp8", "gqa_qkv_norm_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin,
-                              k_cache, v_cache, page_table, old_seq_lens, q_norm_weight, k_norm_weight, eps, rotary_type)
+    return _gqa_qkv_row16_post("chitu_ext_", "gqa_qkv_norm_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
+                               page_table, old_seq_lens, rotary_type, (q_norm_weight, k_norm_weight), _check_head_norm_weights,
+                               lambda: (ptr(q_norm_weight), ptr(k_norm_weight), f32(eps)))
 
 
 def qk_norm_rope(q, k, q_norm_weight, k_norm_weight, eps, cos, sin, rotary_type="hf-llama"):
@@ -677,46 +686,22 @@ def qk_norm_rope(q, k, q_norm_weight, k_norm_weight, eps, cos, sin, rotary_type=
     return out_q, out_k
 
 
-def _gqa_qkv_bias_post(entry, what, qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type):
-    if rotary_type not in ("llama", "hf-llama"):
-        raise ValueError(f"Unknown rotary type: {rotary_type}")
-    require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias)
-    assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
-    assert qkv.stride(2) == 1 and qkv.stride(1) == 128 and qkv.stride(0) % 8 == 0, "dense heads; only the row stride is free"
-    assert bias.dtype == torch.bfloat16 and tuple(bias.shape) == ((q_heads + 2 * kv_heads) * 128,) and bias.is_contiguous()
-    assert k_cache.shape[2] == kv_heads and page_table.dtype == torch.int32 and page_table.stride(1) == 1
-    assert cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and old_seq_lens.dtype == torch.int32
-    bs = qkv.shape[0]
-    assert cos.shape == (bs, 64) and sin.shape == (bs, 64) and page_table.shape[0] >= bs and page_table.is_contiguous()
-    assert old_seq_lens.shape[0] >= bs and old_seq_lens.is_contiguous()
-    check(
-        getattr(_lib.lib(), entry)(
-            ptr(qkv), i64(qkv.stride(0)), i32(q_heads), i32(kv_heads), i32(128), ptr(cos), ptr(sin),
-            i32(0 if rotary_type == "llama" else 1), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
-            ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), ptr(bias), stream_ptr(),
-        ),
-        what,
-    )
-    return qkv[:, :q_heads]
-
-
 def gqa_qkv_bias_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type="llama"):
     """gqa_qkv_post with Qwen2's q / k / v projection bias in front of the rotation, one launch: bias [(q_heads + 2 kv_heads) *
     128] bf16 is added to every row (fp32 add, one bf16 rounding: a bf16 torch.add), q and k heads are then rotated; q in place,
     k and the biased v into the token's page row.  Bit for bit gqa_qkv_post on qkv + bias.  qkv [bs, q_heads + 2*kv_heads, 128]
     bf16 (the row stride may be padded); returns the q view."""
-    assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape and k_cache.dtype == torch.bfloat16
-    assert v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4 and k_cache.shape[3] == 128
-    return _gqa_qkv_bias_post("chitu_ext5_gqa_qkv_bias_post", "gqa_qkv_bias_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
-                              page_table, old_seq_lens, bias, rotary_type)
+    return _gqa_qkv_row16_post("chitu_ext5_", "gqa_qkv_bias_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table,
+                               old_seq_lens, rotary_type, (bias,), lambda b: _check_qkv_bias(b, q_heads + 2 * kv_heads),
+                               lambda: (ptr(bias),))
 
 
 def gqa_qkv_bias_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type="llama"):
     """gqa_qkv_bias_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): the bytes of gqa_kv_quant_fp8 on the
     rows gqa_qkv_bias_post writes.  One launch; returns the q view."""
-    _check_gqa_fp8_caches(k_cache, v_cache)
-    return _gqa_qkv_bias_post("chitu_ext5_gqa_qkv_bias_post_kv_fp8", "gqa_qkv_bias_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin,
-                              k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type)
+    return _gqa_qkv_row16_post("chitu_ext5_", "gqa_qkv_bias_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
+                               page_table, old_seq_lens, rotary_type, (bias,), lambda b: _check_qkv_bias(b, q_heads + 2 * kv_heads),
+                               lambda: (ptr(bias),))
 
 
 def qkv_bias_rope(qkv, q_heads, kv_heads, bias, cos, sin, rotary_type="hf-llama"):
@@ -729,7 +714,7 @@ def qkv_bias_rope(qkv, q_heads, kv_heads, bias, cos, sin, rotary_type="hf-llama"
     require_cuda(qkv, bias, cos, sin)
     assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
     assert qkv.stride(2) == 1 and qkv.stride(1) % 8 == 0 and qkv.stride(0) % 8 == 0
-    assert bias.dtype == torch.bfloat16 and tuple(bias.shape) == ((q_heads + 2 * kv_heads) * 128,) and bias.is_contiguous()
+    _check_qkv_bias(bias, q_heads + 2 * kv_heads)
     T = qkv.shape[0]
     assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
     assert cos.shape == (T, 64) and sin.shape == (T, 64)

@@ -6,7 +6,7 @@ is the one difference: LlamaAttention's qkv_bias branch owns one merged row `bqk
 wqkv; checkpoint.load_checkpoint_hf_llama merges q_proj.bias | k_proj.bias | v_proj.bias per rank) and adds it in the launch
 that already rotates q and k and appends k and v on the decode path (ops.gqa_qkv_bias_post[_kv_fp8]), and in one launch over
 the whole prompt in prefill (ops.qkv_bias_rope: bias, RoPE and the contiguous v -- one launch fewer than a Llama prefill
-layer).  The sum is rounded to bf16 before the rotation (csrc/qkv_bias.hip states the arithmetic).  o_proj and the MLP have
+layer).  The sum is rounded to bf16 before the rotation (csrc/qkv_post_row16.hip states the arithmetic).  o_proj and the MLP have
 no bias.  RoPE is half split ("hf-llama").
 
 Published sizes that run: Qwen2 / Qwen2.5 1.5B, 3B, 7B, 14B, 32B, 72B and DeepSeek-R1-Distill-Qwen 7B / 14B / 32B -- all

@@ -1,4 +1,4 @@
-"""Builders and the CPU oracle of the per-head QK-norm kernels (csrc/qk_norm.hip), in the style of tests/row_exact.py, whose
+"""Builders and the CPU oracle of the per-head QK-norm kernels (csrc/qkv_post_row16.hip), in the style of tests/row_exact.py, whose
 helpers state the two halves: RMSNorm (rms_t, rr_candidates, rms_rows, match_rows) and RoPE (rope_oracle).
 
 One head x of 128 bf16 channels, weight w [128] bf16, eps:
@@ -24,7 +24,9 @@ D = 128
 EPS = 1e-6
 HEAD_EXPS = [-12, -3, 0, 4, 9]
 LIM = 255  # bf16 holds every integer up to 256; 128 * 255^2 = 8 323 200 < 2^24
-SHAPES = [(8, 8), (8, 2), (8, 1), (5, 1), (3, 1)]  # (hq, hkv); the last two leave a wave's four-head group partly empty
+# (hq, hkv); (5, 1) and (3, 1) leave a wave's four-head group partly empty; (32, 8) is Qwen3-8B -- 48 heads, three passes of
+# the decode loop, the k heads in the third: rotated from a prefetched chunk
+SHAPES = [(8, 8), (8, 2), (8, 1), (5, 1), (3, 1), (32, 8)]
 BATCHES = [1, 3, 17]
 PAGES = [16, 48]
 POSITIONS = [0, 1, 5, 77, 300, 2, 1023, 16, 0, 48, 47]

@@ -1,4 +1,4 @@
-"""Builders and the CPU oracle of the q / k / v bias kernels (csrc/qkv_bias.hip), in the style of tests/qk_norm_exact.py.
+"""Builders and the CPU oracle of the q / k / v bias kernels (csrc/qkv_post_row16.hip), in the style of tests/qk_norm_exact.py.
 
 One row of qkv = [hq | hkv | hkv] heads of 128 bf16, bias one bf16 row of the same layout.  For every head:
     y_i = bf16_rne(float(x_i) + float(b_i))                     one add, one rounding
@@ -21,7 +21,9 @@ from tests.qk_norm_exact import fp8_rows, rope_table  # noqa: F401
 from tests.row_exact import BF16, append_oracle, bits, live_row, paged_batch, rope_oracle  # noqa: F401
 
 D = 128
-SHAPES = [(7, 1), (4, 2), (1, 1)]  # (hq, hkv): Qwen2.5-7B at TP 4; two kv heads; a wave with idle head rows
+# (hq, hkv): Qwen2.5-7B at TP 4; two kv heads; a wave with idle head rows; Qwen2.5-7B unsharded -- 36 heads, three passes
+# of the decode loop: the k heads fall in the second and the v heads in the third, on prefetched channels and bias chunks
+SHAPES = [(7, 1), (4, 2), (1, 1), (28, 4)]
 BATCHES = [1, 3, 5]
 PAGE = 16
 OLD_LENS = [0, 15, 16, 17]  # first slot of a page, its last, the next page's first and second

@@ -1,6 +1,6 @@
 """The Qwen2 fixture (tests/golden/qwen2_hf.npz, made by tests/golden/gen_qwen2_hf.py from Hugging Face's Qwen2ForCausalLM), its
 parameters regenerated from the seed, and a plain CPU restatement of this project's arithmetic for one sequence: tests/
-qwen3_ref.py's, with the q / k / v bias added to the bf16 projection (one rounding, csrc/qkv_bias.hip's statement) in place of
+qwen3_ref.py's, with the q / k / v bias added to the bf16 projection (one rounding, csrc/qkv_post_row16.hip's statement) in place of
 the head norm.  The bar against the fixture is tests/qwen3_ref.py::check_logits.  No GPU needed."""
 
 import ast

@@ -1,4 +1,4 @@
-"""The per-head QK-norm kernels (csrc/qk_norm.hip) on the GPU against the CPU oracle of tests/qk_norm_exact.py: the decode form
+"""The per-head QK-norm kernels (csrc/qkv_post_row16.hip) on the GPU against the CPU oracle of tests/qk_norm_exact.py: the decode form
 over bf16 and over fp8 page rows and the prefill form, exact on integer data (every head equals one rr candidate as a whole,
 exactly one page row per live sequence changes, nothing else does), bit-identical to each other on random data, and within
 the project's bar of a float64 norm + RoPE."""

@@ -1,4 +1,4 @@
-"""The q / k / v bias kernels (csrc/qkv_bias.hip) on the GPU against the CPU oracle of tests/qkv_bias_exact.py: the decode form
+"""The q / k / v bias kernels (csrc/qkv_post_row16.hip) on the GPU against the CPU oracle of tests/qkv_bias_exact.py: the decode form
 over bf16 and over fp8 page rows and the prefill form.  Every comparison is bit for bit: q and every cache byte against the
 oracle (poisoned caches between guard pages: exactly one row per live sequence changes), against the existing entry run on the
 bf16 sum qkv + bias, and the three forms against each other."""

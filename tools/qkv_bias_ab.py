@@ -1,4 +1,4 @@
-"""Same-process A/B of the q / k / v bias launches (csrc/qkv_bias.hip) against what they stand beside, Qwen2.5-7B's 28 / 4 heads.
+"""Same-process A/B of the q / k / v bias launches (csrc/qkv_post_row16.hip) against what they stand beside, Qwen2.5-7B's 28 / 4 heads.
 
   decode   chitu_ext5_gqa_qkv_bias_post[_kv_fp8] against chitu_hip_gqa_qkv_post[_kv_fp8] -- the launch the same model without a
            bias takes -- at bs 1 and 16, bf16 and fp8 K / V pages.  The bias entry reads one more 16-byte chunk per lane and head.
