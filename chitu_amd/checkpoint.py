@@ -546,7 +546,28 @@ def load_checkpoint_hf_llama(model, path: str, rank: int = 0, world: int = 1, sk
     st = preprocess_hf_llama(state, args.n_heads, args.n_kv_heads, args.dim, rank, world, mixtral=mixtral,
                              router_row_parallel=False, head_dim=args.head_dim)
     st = to_mixtral_module_names(st, args.num_local_experts) if mixtral else to_llama_module_names(st, qkv_bias=getattr(args, "qkv_bias", False))
+    if getattr(args, "quant", None) == "w8a16":
+        st = llama_to_w8a16(st)
     load_deepseek_v3(model, st)  # the generic strict, shape- and dtype-checked in-place copy
+
+
+_W8A16_LINEAR = re.compile(r"(?:.*\.)?layers\.\d+\.(?:attn\.wqkv|attn\.wo|ffn\.w13|ffn\.w2)$")
+
+
+def llama_to_w8a16(state: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """Module-named tensors of ONE rank -> the same with every layer's wqkv / wo / w13 / w2 quantised for a decoder built with
+    quant="w8a16": int8 rows plus `<name>_scale`, quantize.w8a16.quant_weight_w8a16 of the rank's own merged shard (the row
+    scales of a column-parallel shard are the full matrix's; a row-parallel shard has its own).  The head, the embedding, the
+    norms and bqkv pass through."""
+    from .quantize.w8a16 import quant_weight_w8a16
+
+    out = {}
+    for k, v in state.items():
+        if _W8A16_LINEAR.match(k):
+            out[k], out[k + "_scale"] = quant_weight_w8a16(v)
+        else:
+            out[k] = v
+    return out
 
 
 _QWEN3_MOE_EXPERT = re.compile(r"(?:model\.)?(layers\.\d+)\.mlp\.experts\.(\d+)\.(gate_proj|up_proj|down_proj)\.weight$")

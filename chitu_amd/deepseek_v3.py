@@ -76,6 +76,12 @@ class DeepSeekV3Args:
     # 656-byte rows, the latent as e4m3 with one power-of-two scale per 128 channels, the rope part bf16 (0.569 of the bytes;
     # csrc/mla_kv_fp8.hip).  The cache handed to the decoder is built from cache_manager.mla_kv_layout(kv_cache_dtype).
     kv_cache_dtype: str = "bf16"
+    quant: Optional[str] = None  # the linears are block-fp8 (experts: expert_dtype); LlamaArgs' "w8a16" is refused here
+
+    def __post_init__(self):
+        if self.quant is not None:
+            raise ValueError(f"DeepSeekV3Args: quant={self.quant!r} is not supported (block-fp8 linears; 'w8a16' covers the dense "
+                             "Llama-family decoders)")
 
     def tp_degree(self):
         return self.shard_degree if self.shard_degree is not None else tp.get_tp_size()

@@ -42,10 +42,22 @@ class LlamaArgs:
     # Mistral-7B-v0.1: 4096); None: all of them.  Passed to the attention backend as window_size = (sliding_window - 1, 0).
     sliding_window: Optional[int] = None
     attn_softcap: float = 0.0  # > 0: scores are attn_softcap * tanh(score / attn_softcap) (the backend's softcap); 0.0: off
+    # "w8a16": wqkv, wo, w13 and w2 of every layer are int8 with one fp32 scale per output row (quantize/w8a16.py); None: bf16
+    quant: Optional[str] = None
 
     @property
     def head_dim(self):
         return self.dim // self.n_heads
+
+
+def check_quant_supported(quant, who: str, dense: bool = True) -> None:
+    """The `quant` field of the model args: None, or "w8a16" on the dense Llama-family decoders (Llama, Qwen2, Qwen3)."""
+    if quant is None:
+        return
+    if quant != "w8a16":
+        raise ValueError(f"{who}: quant={quant!r} is not supported (None or 'w8a16')")
+    if not dense:
+        raise ValueError(f"{who}: quant='w8a16' covers the dense Llama-family decoders; this model's linears have their own formats")
 
 
 def precompute_freqs_cis(head_dim: int, max_pos: int, theta: float):
@@ -61,6 +73,23 @@ def _param(*shape, device=None):
     return torch.nn.Parameter(torch.empty(*shape, dtype=torch.bfloat16, device=device), requires_grad=False)
 
 
+def _linear_weight(mod, name, n, k, quant, device):
+    """mod.<name>: the [n, k] weight of a linear -- bf16, or with quant "w8a16" int8 plus the fp32 row scales mod.<name>_scale."""
+    if quant == "w8a16":
+        setattr(mod, name, torch.nn.Parameter(torch.empty(n, k, dtype=torch.int8, device=device), requires_grad=False))
+        setattr(mod, name + "_scale", torch.nn.Parameter(torch.empty(n, dtype=torch.float32, device=device), requires_grad=False))
+    else:
+        setattr(mod, name, _param(n, k, device=device))
+
+
+def _linear(mod, name, x):
+    """x @ mod.<name>^T: the bf16 stream, or the W8A16 one when the weight is int8."""
+    w = getattr(mod, name)
+    if w.dtype == torch.int8:
+        return ops.w8a16_linear(x, w, getattr(mod, name + "_scale"))
+    return ops.bf16_linear(x, w)
+
+
 # Decode batches up to this size run a layer's two residual-add + RMSNorm steps as the prologue of the GEMMs behind
 # them, and RoPE + the K / V page append as the epilogue of the qkv projection (ops.bf16_linear_add_norm[_qkv_post] /
 # bf16_linear_silu_add_norm: bit-identical, three launches fewer per layer).  Measured on Llama-3-8B (tools/llama_ab.py,
@@ -69,10 +98,13 @@ def _param(*shape, device=None):
 FUSE_NORM_MAX_BS = int(os.environ.get("CHITU_FUSE_NORM_MAX_BS", "2"))
 
 
-def _fuses_norm(x, pending, n_out, two_terms_ok: bool = False) -> bool:
+def _fuses_norm(x, pending, n_out, two_terms_ok: bool = False, weight=None) -> bool:
     """pending must be a plain [bs, dim] tensor: not None (first layer), not a partial whose all-reduce the norm launch
     itself performs (tensor_parallel.PendingAllReduce, the in-graph xGMI form).  two_terms_ok: also [bs, 2, dim] (a top-2 MoE's
-    un-summed outputs), for the prologue that takes them (ops.bf16_linear_add_norm)."""
+    un-summed outputs), for the prologue that takes them (ops.bf16_linear_add_norm).  weight: the matrix behind the norm; an int8
+    one (W8A16) has no prologue form and takes the norm launch and the linear separately."""
+    if weight is not None and weight.dtype == torch.int8:
+        return False
     dims_ok = isinstance(pending, torch.Tensor) and (pending.dim() == 2 or (two_terms_ok and pending.dim() == 3 and pending.shape[1] == 2))
     return dims_ok and x.shape[0] <= FUSE_NORM_MAX_BS and ops.bf16_add_norm_fits(x.shape[0], n_out, x.shape[1])
 
@@ -92,8 +124,9 @@ class LlamaAttention(torch.nn.Module):
         self.window_size = (-1, -1) if args.sliding_window is None else (args.sliding_window - 1, 0)
         self.softcap = float(args.attn_softcap)
         # merged [wq | wk | wv] rows (ColumnParallel: heads split across ranks), wo RowParallel
-        self.wqkv = _param((self.hq + 2 * self.hkv) * self.hd, args.dim, device=device)
-        self.wo = _param(args.dim, self.hq * self.hd, device=device)
+        quant = getattr(args, "quant", None)
+        _linear_weight(self, "wqkv", (self.hq + 2 * self.hkv) * self.hd, args.dim, quant, device)
+        _linear_weight(self, "wo", args.dim, self.hq * self.hd, quant, device)
         # Qwen3: an RMSNorm with a learned [head_dim] weight on every q head and every k head, after the projection and before
         # RoPE (replicated under TP: the weights are per channel, not per head)
         self.qk_norm = bool(getattr(args, "qk_norm", False))
@@ -115,7 +148,7 @@ class LlamaAttention(torch.nn.Module):
 
     def decode_forward_paged(self, x, cos, sin, q_len=1):
         """x = attn_norm(h) bf16 [bs, dim] -> wo(attention) before the all-reduce (model.py:167-198)."""
-        return self.decode_from_qkv(ops.bf16_linear(x, self.wqkv), cos, sin, q_len)
+        return self.decode_from_qkv(_linear(self, "wqkv", x), cos, sin, q_len)
 
     def _row_tables(self, q_len):
         """(block table, old length) per row of the step: one row per sequence, or -- a multi-token step, q_len > 1 -- one per
@@ -150,13 +183,13 @@ class LlamaAttention(torch.nn.Module):
                 q.view(bs // q_len, q_len, self.hq, self.hd), k_cache, v_cache, None, None,
                 cache_seqlens=self.cache.get_gpu_multi_seq_lens_incl(), block_table=self.cache.get_gpu_multi_block_table()[::q_len],
                 causal=True, window_size=self.window_size, softcap=self.softcap)
-            return ops.bf16_linear(o.view(bs, self.hq * self.hd), self.wo)
+            return _linear(self, "wo", o.view(bs, self.hq * self.hd))
         table = self.cache.get_gpu_block_table()
         o = self.attn_backend.attn_with_kvcache(
             q.unsqueeze(1), k_cache, v_cache, None, None,
             cache_seqlens=self.cache.get_gpu_seq_lens_incl_this_decode()[:bs], block_table=table[:bs],
             window_size=self.window_size, softcap=self.softcap)
-        return ops.bf16_linear(o.view(bs, self.hq * self.hd), self.wo)
+        return _linear(self, "wo", o.view(bs, self.hq * self.hd))
 
     def decode_from_residual(self, x, pending, norm_weight, eps, cos, sin, q_len=1):
         """Small decode batches: residual add + attn_norm + wqkv projection [+ RoPE and the K / V page append when the
@@ -191,7 +224,7 @@ class LlamaAttention(torch.nn.Module):
         if getattr(varlens, "continued", False):
             return self.prefill_forward_paged(x, cos, sin, varlens)
         T = x.shape[0]
-        qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
+        qkv = _linear(self, "wqkv", x).view(T, self.hq + 2 * self.hkv, self.hd)
         q, k, v = self._rotate(qkv, cos, sin)
         if self.fp8_kv:
             # the pages take the quantised rows (the same index_copy_ scatter, over byte rows); attention runs over the
@@ -202,7 +235,7 @@ class LlamaAttention(torch.nn.Module):
             self.cache.finalize_cache_bylayer_prefill(k, v, self.cache.curr_req_ids, self.cache.curr_varlens, self.layer_id)
         o = self.attn_backend.attn_varlen_func(q, k, v, varlens.prefix_lens, varlens.prefix_lens, varlens.max_len,
                                                varlens.max_len, causal=True, window_size=self.window_size, softcap=self.softcap)
-        return ops.bf16_linear(o.reshape(T, self.hq * self.hd), self.wo)
+        return _linear(self, "wo", o.reshape(T, self.hq * self.hd))
 
     def prefill_forward_paged(self, x, cos, sin, varlens):
         """prefill_forward for tokens behind rows that are already cached (PagedKVCacheManager.prepare_cache_prefill_continue has
@@ -210,14 +243,14 @@ class LlamaAttention(torch.nn.Module):
         attention call over the pages -- every query sees the cached prefix and the new rows up to itself."""
         assert not self.fp8_kv, "continued prefill reads bf16 K / V pages"
         T = x.shape[0]
-        qkv = ops.bf16_linear(x, self.wqkv).view(T, self.hq + 2 * self.hkv, self.hd)
+        qkv = _linear(self, "wqkv", x).view(T, self.hq + 2 * self.hkv, self.hd)
         q, k, v = self._rotate(qkv, cos, sin)
         self.cache.finalize_cache_bylayer_prefill_continue(k, v, self.layer_id)
         k_cache, v_cache = self.cache.get_paged_kv_cache(self.layer_id)
         o = self.attn_backend.attn_varlen_with_kvcache(
             q, k_cache, v_cache, varlens.prefix_lens, self.cache.get_gpu_continue_seq_lens_incl(),
             self.cache.get_gpu_continue_block_table(), varlens.max_len, causal=True, window_size=self.window_size, softcap=self.softcap)
-        return ops.bf16_linear(o.reshape(T, self.hq * self.hd), self.wo)
+        return _linear(self, "wo", o.reshape(T, self.hq * self.hd))
 
 
 class LlamaFeedForward(torch.nn.Module):
@@ -227,10 +260,13 @@ class LlamaFeedForward(torch.nn.Module):
         super().__init__()
         t = tp.get_tp_size()
         self.inter = args.ffn_dim // t
-        self.w13 = _param(2 * self.inter, args.dim, device=device)
-        self.w2 = _param(args.dim, self.inter, device=device)
+        quant = getattr(args, "quant", None)
+        _linear_weight(self, "w13", 2 * self.inter, args.dim, quant, device)
+        _linear_weight(self, "w2", args.dim, self.inter, quant, device)
 
     def forward(self, x):
+        if self.w13.dtype == torch.int8:
+            return _linear(self, "w2", ops.w8a16_linear_silu(x, self.w13, self.w13_scale))
         return ops.bf16_linear(ops.bf16_linear_silu(x, self.w13), self.w2)
 
 
@@ -248,7 +284,7 @@ class LlamaBlock(torch.nn.Module):
     def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
         """(x, pending) -> (x', pending'): residual adds folded into the RMSNorm that consumes them;
         varlens given = prefill; q_len > 1: the rows are q_len tokens per sequence (LlamaDecoder.decode_multi)."""
-        if varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0]):
+        if varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0], weight=self.attn.wqkv):
             # small decode batches: the add + norm run as the prologue of the projection that consumes them
             x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin, q_len)
             a = tp.defer_all_reduce(a)
@@ -261,7 +297,7 @@ class LlamaBlock(torch.nn.Module):
         return self.ffn_part(x, a, varlens)
 
     def ffn_part(self, x, a, varlens):
-        if varlens is None and _fuses_norm(x, a, self.ffn.inter):
+        if varlens is None and _fuses_norm(x, a, self.ffn.inter, weight=self.ffn.w13):
             x, h = ops.bf16_linear_silu_add_norm(x, a, self.ffn_norm, self.eps, self.ffn.w13)
             return x, tp.defer_all_reduce(ops.bf16_linear(h, self.ffn.w2))
         x, hn = tp.add_norm(x, a, self.ffn_norm, self.eps)[:2]
@@ -278,6 +314,7 @@ class LlamaDecoder(torch.nn.Module):
         super().__init__()
         self.args, self.cache, self.attn_backend, self.device = args, cache, attn_backend, torch.device(device)
         t = tp.get_tp_size()
+        check_quant_supported(getattr(args, "quant", None), type(self).__name__)
         assert args.vocab_size % t == 0 and args.n_kv_heads % t == 0 and args.head_dim == 128, "gqa_decode: head_dim 128"
         # the cache this decoder was handed must have the format its args name (gqa_kv_layout raises on an unknown name)
         # in both modes: a bf16 cache of another row shape or dtype used to fail at the first attention assert, it fails here now.

@@ -36,6 +36,12 @@ class MixtralArgs:
     kv_cache_dtype: str = "bf16"  # "fp8": see LlamaArgs.kv_cache_dtype
     sliding_window: Optional[int] = None  # see LlamaArgs.sliding_window
     attn_softcap: float = 0.0  # see LlamaArgs.attn_softcap
+    quant: Optional[str] = None  # the experts are W8A8 already; LlamaArgs' "w8a16" (dense linears) is refused here
+
+    def __post_init__(self):
+        if self.quant is not None:
+            raise ValueError(f"MixtralArgs: quant={self.quant!r} is not supported (the experts are int8 W8A8; 'w8a16' covers the dense "
+                             "Llama-family decoders)")
 
     @property
     def head_dim(self):

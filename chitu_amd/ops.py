@@ -1202,3 +1202,102 @@ def absorb_uv_quant_fp8(x, w, scale, scale_offset, scale_stride_h, scale_stride_
         "absorb_uv_quant_fp8",
     )
     return q, s
+
+
+# ---------------------------------------------------------------- W8A16 weight-only int8 linears (include/chitu_hip_ext6.h)
+def w8a16_tiled(M: int, n_rows: int, K: int) -> bool:
+    """True where a W8A16 linear over `n_rows` weight rows takes the widen + tiled-GEMM + scale_round form: prefill-sized M,
+    where the streaming kernel would read the weights once per 32 rows.  Started at chitu_hip_bf16_gemm's own rule
+    (csrc/gate.hip: M >= 256, or M >= 128 with >= 1024 rows) and moved by measurement (tools/w8a16_ab.py --sweep,
+    profiles/w8a16_ab.txt): at 128 tokens the widen launch still costs more than it saves on 4096-row matrices (tiled / stream
+    1.09 - 1.19) and wins from 6144 rows on (0.61 - 0.68); at 192 tokens it wins everywhere (0.48 - 0.81).  Every M this
+    returns True for lies inside the bf16 rule, so the GEMM over the widened weights is the compute-shaped one."""
+    return (M >= 256 or (M >= 192 and n_rows >= 1024) or (M >= 128 and n_rows >= 6144)) and K < (1 << 23)
+
+
+def w8a16_plan(M: int, N: int, K: int, silu: bool = False):
+    """Mirror of the host's launch plan for w8a16_linear (N = output columns) / w8a16_linear_silu (N = inter): the form
+    ("stream" or "tiled") and, for the streaming form, one (MT, WK, ring depth) per 32-row launch -- the template arguments of
+    w8a16_gemm_kernel / w8a16_gemm_silu_kernel and the depth of their register ring (csrc/w8a16_gemm.hip)."""
+    if M <= 0:
+        return {"form": "none", "launches": []}
+    if w8a16_tiled(M, 2 * N if silu else N, K):
+        return {"form": "tiled", "launches": []}
+    tiles, nb, wk = (N + 15) // 16, K // 128 + (1 if K % 128 else 0), 8
+    while wk > 1 and (wk > nb or tiles * wk > 4096):
+        wk >>= 1
+    launches = []
+    for mb in range(0, M, 32):
+        mt = 1 if M - mb <= 16 else 2
+        launches.append((mt, wk, (2 if mt == 2 else 3) if silu else (2 if mt == 2 else 4)))
+    return {"form": "stream", "launches": launches}
+
+
+_W8A16_TILED_ROWS = 4096  # token rows per tiled GEMM call: bounds the fp32 accumulator scratch of a long prompt
+
+
+def _w8a16_check(x, q_weight, scale):
+    require_cuda(x, q_weight, scale)
+    assert x.dtype == torch.bfloat16 and q_weight.dtype == torch.int8 and scale.dtype == torch.float32
+    assert x.is_contiguous() and q_weight.is_contiguous() and scale.is_contiguous()
+    assert q_weight.dim() == 2 and q_weight.shape[1] == x.shape[-1] and scale.numel() == q_weight.shape[0]
+
+
+def w8a16_widen(q_weight: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """bf16(q), exact and unscaled: the weight operand of the tiled bf16 GEMM.  out: bf16 [N, K] to fill (the workspace)."""
+    require_cuda(q_weight)
+    assert q_weight.dtype == torch.int8 and q_weight.dim() == 2 and q_weight.is_contiguous()
+    N, K = q_weight.shape
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=q_weight.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == N * K
+    check(_lib.lib().chitu_ext6_w8a16_widen(ptr(q_weight), ptr(out), i64(N), i64(K), stream_ptr()), "w8a16_widen")
+    return out
+
+
+def _w8a16_tiled(x2, q_weight, scale, out2, silu):
+    """x2 [M, K], out2 [M, N or inter]: q widened once into the per-device workspace (sized by the largest linear seen), then per
+    block of token rows the compute-shaped bf16 GEMM with an fp32 output and the scale-and-round launch."""
+    rows, K = q_weight.shape
+    M = x2.shape[0]
+    wide = workspace.get(rows * K * 2, x2.device, "w8a16_wide")[: rows * K * 2].view(torch.bfloat16).view(rows, K)
+    w8a16_widen(q_weight, wide)
+    for m0 in range(0, M, _W8A16_TILED_ROWS):
+        xb, ob = x2[m0 : m0 + _W8A16_TILED_ROWS], out2[m0 : m0 + _W8A16_TILED_ROWS]
+        acc = bf16_linear(xb, wide, out_dtype=torch.float32)
+        check(_lib.lib().chitu_ext6_w8a16_scale_round(ptr(acc), ptr(scale), ptr(ob), float_dtype_code(ob.dtype), i64(xb.shape[0]),
+                                                      i64(ob.shape[1]), i32(1 if silu else 0), stream_ptr()), "w8a16_scale_round")
+
+
+def w8a16_linear(x: torch.Tensor, q_weight: torch.Tensor, scale: torch.Tensor, out_dtype=None) -> torch.Tensor:
+    """F.linear(x, dequant(q_weight, scale)) with the scale on the fp32 accumulator: out = round((x q^T) * scale), q_weight
+    int8 [N, K] ([out, in]), scale fp32 [N].  Decode batches stream the int8 weights (half the bytes of bf16_linear); from
+    w8a16_tiled's token count on the weights are widened once and the tiled bf16 GEMM runs over them."""
+    _w8a16_check(x, q_weight, scale)
+    K = x.shape[-1]
+    M = x.numel() // K
+    N = q_weight.shape[0]
+    out = torch.empty(*x.shape[:-1], N, dtype=out_dtype or torch.bfloat16, device=x.device)
+    if w8a16_tiled(M, N, K):
+        _w8a16_tiled(x.reshape(M, K), q_weight, scale, out.view(M, N), False)
+        return out
+    check(_lib.lib().chitu_ext6_w8a16_gemm(ptr(x), ptr(q_weight), ptr(scale), ptr(out), float_dtype_code(out.dtype), i64(M), i64(N),
+                                           i64(K), stream_ptr()), "w8a16_linear")
+    return out
+
+
+def w8a16_linear_silu(x: torch.Tensor, q_w13: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """silu(x w1^T) * (x w3^T) for q_w13 = [w1; w3] int8 [2 inter, K], scale fp32 [2 inter]: bf16_linear_silu's rounding chain
+    on the scaled fp32 accumulators, one launch at decode batch sizes."""
+    _w8a16_check(x, q_w13, scale)
+    K = x.shape[-1]
+    inter = q_w13.shape[0] // 2
+    assert q_w13.shape[0] == 2 * inter
+    M = x.numel() // K
+    out = torch.empty(*x.shape[:-1], inter, dtype=torch.bfloat16, device=x.device)
+    if w8a16_tiled(M, 2 * inter, K):
+        _w8a16_tiled(x.reshape(M, K), q_w13, scale, out.view(M, inter), True)
+        return out
+    check(_lib.lib().chitu_ext6_w8a16_gemm_silu(ptr(x), ptr(q_w13), ptr(scale), ptr(out), i64(M), i64(inter), i64(K), stream_ptr()),
+          "w8a16_linear_silu")
+    return out

@@ -42,6 +42,7 @@ class Qwen2Args:
     attn_softcap: float = 0.0
     qkv_bias: bool = True
     tie_word_embeddings: bool = False
+    quant: Optional[str] = None  # "w8a16": int8 wqkv / wo / w13 / w2 (LlamaArgs.quant); the reference's shipped W8A16 model is Qwen2-7B
 
     @property
     def head_dim(self):

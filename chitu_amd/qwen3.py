@@ -36,6 +36,7 @@ class Qwen3Args:
     attn_softcap: float = 0.0
     qk_norm: bool = True
     tie_word_embeddings: bool = False
+    quant: Optional[str] = None  # "w8a16": int8 wqkv / wo / w13 / w2 (LlamaArgs.quant)
 
 
 class Qwen3Block(LlamaBlock):

@@ -52,6 +52,12 @@ class Qwen3MoeArgs:
     tie_word_embeddings: bool = False
     mlp_only_layers: List[int] = field(default_factory=list)  # dense layers: none in any published size, refused
     decoder_sparse_step: int = 1  # every layer is sparse in every published size; anything else is refused
+    quant: Optional[str] = None  # the experts are bf16; LlamaArgs' "w8a16" (dense linears) is refused here
+
+    def __post_init__(self):
+        if self.quant is not None:
+            raise ValueError(f"Qwen3MoeArgs: quant={self.quant!r} is not supported ('w8a16' covers the dense Llama-family decoders; "
+                             "W8A16 experts are not built)")
 
 
 def check_args(args: Qwen3MoeArgs, tp_size: int = 1) -> None:

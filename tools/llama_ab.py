@@ -3,11 +3,17 @@
     python tools/llama_ab.py [--steps 40] [--reps 2] [--bs 1,2,4]
 Variants: the two add + RMSNorm launches of a layer as their own kernels (fuse 0) vs as the prologue of the GEMM behind
 them (ops.bf16_linear_add_norm / bf16_linear_silu_add_norm), and any launch-variant overrides given as
---opt name=value (chitu_amd._lib.DEBUG_OPTIONS), each measured with and without the fusion."""
+--opt name=value (chitu_amd._lib.DEBUG_OPTIONS), each measured with and without the fusion.
+
+    python tools/llama_ab.py --w8a16 [--bs 1,16] [--out FILE]
+instead: the whole step of the bf16 decoder against the W8A16 one (quantize.quantize_w8a16_: int8 wqkv / wo / w13 / w2), each
+(format, batch size) in a fresh child process under its own time limit, one after the other (this process never opens the
+GPU); a child that fails ends the run.  Prints one JSON line per child and the step-time ratios."""
 import argparse
 import contextlib
 import json
 import os
+import subprocess
 import sys
 
 import torch
@@ -26,7 +32,31 @@ def main():
     ap.add_argument("--ctx", type=int, default=1024)
     ap.add_argument("--bs", default="1")
     ap.add_argument("--opt", action="append", default=[], help="name=value launch-variant override, measured as its own variant")
+    ap.add_argument("--w8a16", action="store_true", help="whole-step A/B of the bf16 and the W8A16 decoder, fresh child processes")
+    ap.add_argument("--child-format", default="", help=argparse.SUPPRESS)
+    ap.add_argument("--child-timeout", type=int, default=300, help="seconds per child")
+    ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.w8a16:
+        rows = {}
+        for bs in [int(b) for b in a.bs.split(",")]:
+            for fmt in ("bf16", "w8a16"):
+                cmd = ["timeout", "-k", "10", str(a.child_timeout), sys.executable, os.path.abspath(__file__), "--child-format", fmt,
+                       "--bs", str(bs), "--steps", str(a.steps), "--warmup", str(a.warmup), "--ctx", str(a.ctx)]
+                res = subprocess.run(cmd, capture_output=True, text=True)
+                line = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
+                if res.returncode != 0 or not line:
+                    print(res.stdout[-2000:], res.stderr[-2000:])
+                    sys.exit(f"the {fmt} bs {bs} child ended with status {res.returncode}: nothing more is started")
+                rows[f"{fmt} bs{bs}"] = json.loads(line[-1])
+                print(line[-1], flush=True)
+            rows[f"ratio_w8a16_over_bf16 bs{bs}"] = round(rows[f"w8a16 bs{bs}"]["ms_per_step"] / rows[f"bf16 bs{bs}"]["ms_per_step"], 4)
+            print(f"bs {bs}: bf16 {rows[f'bf16 bs{bs}']['ms_per_step']} ms -> w8a16 {rows[f'w8a16 bs{bs}']['ms_per_step']} ms, ratio "
+                  f"{rows[f'ratio_w8a16_over_bf16 bs{bs}']}", flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(rows, f, indent=1)
+        return
     from chitu_amd.attn_backend import HipAttnBackend
     from chitu_amd.cache_manager import PagedKVCacheManager
 
@@ -39,6 +69,18 @@ def main():
     llama.init_synthetic_(model, seed=3)
     cache.paged_k_cache.normal_(0, 0.5)
     cache.paged_v_cache.normal_(0, 0.5)
+    if a.child_format:
+        if a.child_format == "w8a16":
+            from chitu_amd.quantize import quantize_w8a16_
+
+            quantize_w8a16_(model)
+            torch.cuda.empty_cache()
+        bs = int(a.bs)
+        dt = bench.measure(model, cache, bs, a.ctx, a.steps, a.warmup, 1, True, "c_")
+        weights = sum(p.numel() * p.element_size() for n, p in model.named_parameters() if ".attn.w" in n or ".ffn.w" in n)
+        print(json.dumps({"format": a.child_format, "bs": bs, "ctx": a.ctx, "ms_per_step": round(dt / a.steps * 1e3, 4),
+                          "layer_weight_GB": round(weights / 1e9, 3)}), flush=True)
+        return
     variants = [("norm launches", 0, None), ("norm in GEMM prologue", 4, None)]
     for o in a.opt:
         name, val = o.split("=")
