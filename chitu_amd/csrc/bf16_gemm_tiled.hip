@@ -6,7 +6,7 @@
 // Replaces (reference, read-only), for M >= 128: torch.nn.functional.linear on bf16 weights as used by
 //   chitu/models/model_deepseek_v3.py:810-812  GateDeepSeekV3.forward  (scores = linear(x, weight))
 //   chitu/models/model.py:104-132, 201-214     Attention / FeedForward projections in prefill
-// The skinny kernel (gate.hip: bf16_gemm_kernel) streams the weight matrix once per 32 token rows: 64 launches of
+// The skinny kernel (bf16_gemm.hip: bf16_gemm_kernel) streams the weight matrix once per 32 token rows: 64 launches of
 // 4.7 us for the router of a 2048-token prompt (profiles/r02_prefill_*), one launch here.
 #include "common.h"
 #include "gemm_common.h"
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-// chitu_hip_bf16_gemm's large-M form (declared in gemm_common.h, called from gate.hip)
+// chitu_hip_bf16_gemm's large-M form (declared in gemm_common.h, called from bf16_gemm.hip)
 void launch_bf16_gemm_tiled(const bf16_t* x, const bf16_t* w, void* out, int out_dt, int64_t M, int64_t N, int64_t K,
                             int num_splits, float* partials, hipStream_t st) {
     // 64-token tiles while 128-token ones would leave CUs with fewer than two workgroups (fp8_gemm_tiled.hip has the sweep);

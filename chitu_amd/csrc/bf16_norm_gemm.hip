@@ -16,10 +16,11 @@
 // form: per-chunk sequential sum, wave butterfly, the 16 wave sums in order), the normalised rows go to LDS as
 // bf16, and the K loop takes its activation fragments from there (all 16 MFMA columns of a token read one address:
 // a broadcast).  Workgroup 0 also writes the new residual stream.  Same K split, same MFMA order as
-// bf16_gemm_kernel / bf16_gemm_silu_kernel (gate.hip): results are BIT-IDENTICAL to the unfused launches.
+// bf16_gemm_kernel / bf16_gemm_silu_kernel (bf16_gemm.hip): results are BIT-IDENTICAL to the unfused launches.
 #include "common.h"
 #include "gemm_common.h"
 #include "norm_common.h"
+#include "stream_gemm.h"
 
 namespace chitu {
 
@@ -179,7 +180,7 @@ struct QkvPostArgs {
 };
 
 // ---------------------------------------------------------------- add + norm -> out = y . W^T
-// K loop, K split and accumulation order of bf16_gemm_kernel<1, WK> (gate.hip); D = ring depth (8: the wave's whole
+// K loop, K split and accumulation order of bf16_gemm_kernel<1, WK> (bf16_gemm.hip); D = ring depth (8: the wave's whole
 // K range in one round trip, the form chitu_hip_bf16_gemm picks for <= 8 blocks per wave).
 // POUT: the owner workgroup also leaves the normalised rows / their fp8 form (NormOut).  S > 1 (grid.y): K cut over S
 // workgroups per tile, fp32 partial planes [S][M][N] for the consumer to sum in plane order (chitu_hip_bf16_gemm's
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(64 * WK) void bf16_gemm_add_norm_kernel(
             }
         }
     }
-    f32x4 acc[1] = {f32x4{e0[0] + o0[1], e0[2] + o0[3], e1[0] + o1[1], e1[2] + o1[3]}};
+    f32x4 acc[1] = {fold_halves(e0, o0, e1, o1)};
     if (!QKV) {
         gemm_epilogue_v2<1, WK>(acc, red, out, out_dt, partial, M, N, S, 0, n0);
         return;
@@ -314,7 +315,8 @@ __global__ __launch_bounds__(64 * WK) void bf16_gemm_add_norm_kernel(
 }
 
 // ---------------------------------------------------------------- add + norm -> h = silu(y . W1^T) * (y . W3^T)
-// K loop, K split, accumulation order and epilogue of bf16_gemm_silu_kernel<1, WK> (gate.hip), ring depth 3.
+// K loop, K split, accumulation order and epilogue of bf16_gemm_silu_kernel<1, WK> (bf16_gemm.hip), ring depth 3.
+// The K split on the host is stream_wk, the unfused launches' own: fused and unfused accumulate in the same order.
 template <int WK, int MR>
 __global__ __launch_bounds__(64 * WK) __attribute__((amdgpu_waves_per_eu(MR == 1 ? 4 : 2, 8))) void bf16_gemm_silu_add_norm_kernel(
     const bf16_t* x, int64_t x_stride, const bf16_t* add, int64_t add_stride, bf16_t* sum_out, int64_t sum_stride,
@@ -380,8 +382,8 @@ __global__ __launch_bounds__(64 * WK) __attribute__((amdgpu_waves_per_eu(MR == 1
             }
         }
     }
-    f32x4 ag = {ge0[0] + go0[1], ge0[2] + go0[3], ge1[0] + go1[1], ge1[2] + go1[3]};
-    f32x4 au = {ue0[0] + uo0[1], ue0[2] + uo0[3], ue1[0] + uo1[1], ue1[2] + uo1[3]};
+    f32x4 ag = fold_halves(ge0, go0, ge1, go1), au = fold_halves(ue0, uo0, ue1, uo1);
+    // silu_reduce_store<1, WK> (stream_gemm.h), written out: through the call this launch's machine code changes
     if (WK > 1) {
         *reinterpret_cast<f32x4*>(&red[(wave * 128 + lane) * 4]) = ag;
         *reinterpret_cast<f32x4*>(&red[(wave * 128 + 64 + lane) * 4]) = au;
@@ -418,14 +420,6 @@ __global__ __launch_bounds__(64 * WK) __attribute__((amdgpu_waves_per_eu(MR == 1
     }
 }
 
-// the K split chitu_hip_bf16_gemm / chitu_hip_bf16_gemm_silu would pick for this shape (kept in step with gate.hip so
-// the fused and the unfused launches accumulate in the same order)
-static int gemm_wk(int tiles, int KB) {
-    int WK = 8;
-    while (WK > 1 && (WK > KB || (int64_t)tiles * WK > 4096)) WK >>= 1;
-    return WK;
-}
-
 // Do the bf16 rows [M][cols] at a (row stride a_stride) and at b (b_stride) share a byte?  sum_out is written by workgroup 0
 // while every other workgroup of the grid still reads x and add for its own copy of the prologue: a sum_out inside either
 // would hand the later workgroups the NEW residual stream as their input.  (chitu_hip_rmsnorm can run in place: there one
@@ -456,7 +450,7 @@ extern "C" int chitu_hip_bf16_gemm_add_norm(const void* x_bf16, int64_t x_row_st
     if (M == 0) return CHITU_OK;
     if (!fused_norm_shape_ok(M, K)) return CHITU_ERR_UNSUPPORTED;
     const int KB = (int)(K / 64), tiles = (int)((N + 15) / 16);
-    const int WK = gemm_wk(tiles, KB);
+    const int WK = stream_wk(tiles, KB);
     if (WK < 4) return CHITU_ERR_UNSUPPORTED;
     const int per_wave = KB / WK;
     // (after the shape limits: an unfit shape is CHITU_ERR_UNSUPPORTED whatever its pointers)
@@ -510,7 +504,7 @@ extern "C" int chitu_hip_bf16_gemm_add_norm_qkv_post(
     const int64_t N = (int64_t)(q_heads + 2 * kv_heads) * head_dim;
     if (!fused_norm_shape_ok(M, K) || head_dim % 16 != 0 || N >= (1 << 30)) return CHITU_ERR_UNSUPPORTED;
     const int KB = (int)(K / 64), tiles = (int)(N / 16);
-    const int WK = gemm_wk(tiles, KB);
+    const int WK = stream_wk(tiles, KB);
     if (WK < 4) return CHITU_ERR_UNSUPPORTED;
     const int per_wave = KB / WK;
     // (after the shape limits: an unfit shape is CHITU_ERR_UNSUPPORTED whatever its pointers)
@@ -561,7 +555,7 @@ extern "C" int chitu_hip_bf16_gemm_silu_add_norm(const void* x_bf16, int64_t x_r
     if (M == 0) return CHITU_OK;
     if (!fused_norm_shape_ok(M, K)) return CHITU_ERR_UNSUPPORTED;
     const int KB = (int)(K / 64), tiles = (int)((inter + 15) / 16);
-    const int WK = gemm_wk(tiles, KB);
+    const int WK = stream_wk(tiles, KB);
     if (WK < 4) return CHITU_ERR_UNSUPPORTED;
     // (after the shape limits: an unfit shape is CHITU_ERR_UNSUPPORTED whatever its pointers)
     CHITU_REQUIRE(!rows_overlap(sum_out_bf16, sum_row_stride, K, x_bf16, x_row_stride, K, M) &&

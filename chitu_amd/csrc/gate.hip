@@ -1,4 +1,4 @@
-// MoE router for decode on gfx950: skinny bf16 GEMM (scores) + one fused routing kernel.
+// MoE router for decode on gfx950: the fused routing kernels behind the score GEMM (bf16_gemm.hip).
 //
 // Replaces (reference, read-only) GateDeepSeekV3.forward, chitu/models/model_deepseek_v3.py:810-842,
 // which runs as ~17 small torch launches per layer (F.linear, sigmoid, + bias, view, topk(2), sum,
@@ -11,217 +11,12 @@
 // weight sum, division, scaling).  Ties are broken towards the LOWER index (torch.topk leaves tie
 // order unspecified), which makes routing deterministic.
 //
-// The score GEMM is the same weight-streaming shape as fp8_gemm.hip with bf16 weights as the MFMA A
-// operand; N = n_experts is tiny (16 row tiles), so K is split across workgroups and the fp32
-// partials are summed, in order, by the routing kernel itself (no separate reduce launch).  The same
-// GEMM entry point serves the LM head (N = vocab/tp, no split).
+// The score GEMM (chitu_hip_bf16_gemm, num_splits > 1) leaves fp32 partial planes of its K split; the
+// routing kernels here sum them, in plane order, themselves (no separate reduce launch).
 #include "common.h"
-#include "gemm_common.h"
 #include "moe_align_device.h"
 
 namespace chitu {
-
-// ---------------------------------------------------------------- skinny bf16 GEMM
-// out[m][n] = sum_k x[m][k] * w[n][k]; k-block = 64 elements = one 128-B line of a weight row.
-// Full-line layout (gemm_common.h): lane (j, g) loads 16 B of weight row n0 + 8*half + j/2 at element
-// ((j%2)*4 + g)*8 of the block, so a wave-load takes whole lines from 8 rows; MFMA A-row j then holds
-// K elements [0,32) (even j) or [32,64) (odd j) of weight row j/2, the block product is taken with the
-// two activation fragments x[0..31], x[32..63] and the halves are added in-lane at the end.  bf16 has no
-// per-block scales, so the four accumulators run across the whole K range.
-template <int MT>
-struct Bf16Stage {
-    s16x8 w[2];
-    s16x8 x[MT][2];
-};
-
-template <int MT, int WK, bool DEEP = false>
-__global__ __launch_bounds__(64 * WK) void bf16_gemm_kernel(const bf16_t* __restrict__ X,
-                                                            const bf16_t* __restrict__ W,
-                                                            void* __restrict__ out, int out_dt,
-                                                            float* __restrict__ partial, int M, int N,
-                                                            int K, int S, int m_base) {
-    __shared__ float red[WK > 1 ? WK * MT * 256 : 1];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: SGPR index math
-    const int j = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * 16;
-    const int KB = K >> 6;
-    const int T = S * WK;
-    const int t = blockIdx.y * WK + wave;
-    const int kb0 = (int)((long)KB * t / T), kb1 = (int)((long)KB * (t + 1) / T);
-    const int eoff = ((j & 1) * 4 + g) * 8;
-    const bf16_t* wp0 = W + (size_t)min(n0 + (j >> 1), N - 1) * K + eoff;
-    const bf16_t* wp1 = W + (size_t)min(n0 + 8 + (j >> 1), N - 1) * K + eoff;
-    const bf16_t* xp[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) xp[mt] = X + (size_t)min(m_base + mt * 16 + j, M - 1) * K + g * 8;
-    f32x4 e0[MT], o0[MT], e1[MT], o1[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) e0[mt] = o0[mt] = e1[mt] = o1[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto load = [&](Bf16Stage<MT>& st, int kb) {
-        const int off = kb << 6;
-        st.w[0] = __builtin_nontemporal_load(reinterpret_cast<const s16x8*>(wp0 + off));
-        st.w[1] = __builtin_nontemporal_load(reinterpret_cast<const s16x8*>(wp1 + off));
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            st.x[mt][0] = *reinterpret_cast<const s16x8*>(xp[mt] + off);
-            st.x[mt][1] = *reinterpret_cast<const s16x8*>(xp[mt] + off + 32);
-        }
-    };
-    auto compute = [&](const Bf16Stage<MT>& st) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            e0[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.w[0], st.x[mt][0], e0[mt], 0, 0, 0);
-            o0[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.w[0], st.x[mt][1], o0[mt], 0, 0, 0);
-            e1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.w[1], st.x[mt][0], e1[mt], 0, 0, 0);
-            o1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.w[1], st.x[mt][1], o1[mt], 0, 0, 0);
-        }
-    };
-    // DEEP (single token tile, <= 8 K blocks per wave): the wave's whole K range in one round trip
-    // (a ring of 8 for the long-K form was measured: slower, Llama-3-8B bs 1 3.46 -> 3.50 ms/step)
-    constexpr int D = DEEP ? 8 : MT >= 4 ? 2 : 4;
-    Bf16Stage<MT> ring[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-        if (kb0 + d < kb1) load(ring[d], kb0 + d);
-    for (int kb = kb0; kb < kb1; kb += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (kb + d < kb1) {
-                compute(ring[d]);
-                if (kb + d + D < kb1) load(ring[d], kb + d + D);
-            }
-        }
-    }
-    f32x4 acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-        acc[mt] = f32x4{e0[mt][0] + o0[mt][1], e0[mt][2] + o0[mt][3], e1[mt][0] + o1[mt][1], e1[mt][2] + o1[mt][3]};
-    gemm_epilogue_v2<MT, WK>(acc, red, out, out_dt, partial, M, N, S, m_base, n0);
-}
-
-// Gate/up projection of an unquantised SwiGLU MLP with SiluAndMul in the epilogue: W = [w1 | w3] rows
-// (2*inter x K); a wave owns gate tile [n0, n0+16) and up tile [inter+n0, inter+n0+16), shares the
-// activation fragments between them and writes h = bf16(bf16(silu(bf16(g))) * bf16(u)) -- FeedForward
-// (models/model.py:212-214: F.silu(w1 x) * w3 x, every torch op rounding once) in one launch.
-template <int MT>
-struct Bf16Stage2 {
-    s16x8 wg[2], wu[2];
-    s16x8 x[MT][2];
-};
-
-template <int MT, int WK>
-__global__ __launch_bounds__(64 * WK) void bf16_gemm_silu_kernel(const bf16_t* __restrict__ X, const bf16_t* __restrict__ W,
-                                                                 bf16_t* __restrict__ out, int M, int inter, int K,
-                                                                 int m_base) {
-    __shared__ float red[WK > 1 ? WK * MT * 512 : 1];
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: SGPR index math
-    const int j = lane & 15, g = lane >> 4;
-    const int n0 = blockIdx.x * 16;
-    const int KB = K >> 6;
-    const int kb0 = KB * wave / WK, kb1 = KB * (wave + 1) / WK;
-    const int eoff = ((j & 1) * 4 + g) * 8;
-    const int r0 = min(n0 + (j >> 1), inter - 1), r1 = min(n0 + 8 + (j >> 1), inter - 1);
-    const bf16_t* gp0 = W + (size_t)r0 * K + eoff;
-    const bf16_t* gp1 = W + (size_t)r1 * K + eoff;
-    const bf16_t* up0 = W + (size_t)(inter + r0) * K + eoff;
-    const bf16_t* up1 = W + (size_t)(inter + r1) * K + eoff;
-    const bf16_t* xp[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) xp[mt] = X + (size_t)min(m_base + mt * 16 + j, M - 1) * K + g * 8;
-    f32x4 ge0[MT], go0[MT], ge1[MT], go1[MT], ue0[MT], uo0[MT], ue1[MT], uo1[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-        ge0[mt] = go0[mt] = ge1[mt] = go1[mt] = ue0[mt] = uo0[mt] = ue1[mt] = uo1[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto load = [&](Bf16Stage2<MT>& st, int kb) {
-        const int off = kb << 6;
-        st.wg[0] = __builtin_nontemporal_load(reinterpret_cast<const s16x8*>(gp0 + off));
-        st.wg[1] = __builtin_nontemporal_load(reinterpret_cast<const s16x8*>(gp1 + off));
-        st.wu[0] = __builtin_nontemporal_load(reinterpret_cast<const s16x8*>(up0 + off));
-        st.wu[1] = __builtin_nontemporal_load(reinterpret_cast<const s16x8*>(up1 + off));
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            st.x[mt][0] = *reinterpret_cast<const s16x8*>(xp[mt] + off);
-            st.x[mt][1] = *reinterpret_cast<const s16x8*>(xp[mt] + off + 32);
-        }
-    };
-    auto compute = [&](const Bf16Stage2<MT>& st) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            ge0[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wg[0], st.x[mt][0], ge0[mt], 0, 0, 0);
-            go0[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wg[0], st.x[mt][1], go0[mt], 0, 0, 0);
-            ge1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wg[1], st.x[mt][0], ge1[mt], 0, 0, 0);
-            go1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wg[1], st.x[mt][1], go1[mt], 0, 0, 0);
-            ue0[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wu[0], st.x[mt][0], ue0[mt], 0, 0, 0);
-            uo0[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wu[0], st.x[mt][1], uo0[mt], 0, 0, 0);
-            ue1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wu[1], st.x[mt][0], ue1[mt], 0, 0, 0);
-            uo1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(st.wu[1], st.x[mt][1], uo1[mt], 0, 0, 0);
-        }
-    };
-    constexpr int D = MT >= 2 ? 2 : 3;
-    Bf16Stage2<MT> ring[D];
-#pragma unroll
-    for (int d = 0; d < D; ++d)
-        if (kb0 + d < kb1) load(ring[d], kb0 + d);
-    for (int kb = kb0; kb < kb1; kb += D) {
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (kb + d < kb1) {
-                compute(ring[d]);
-                if (kb + d + D < kb1) load(ring[d], kb + d + D);
-            }
-        }
-    }
-    f32x4 ag[MT], au[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        ag[mt] = f32x4{ge0[mt][0] + go0[mt][1], ge0[mt][2] + go0[mt][3], ge1[mt][0] + go1[mt][1], ge1[mt][2] + go1[mt][3]};
-        au[mt] = f32x4{ue0[mt][0] + uo0[mt][1], ue0[mt][2] + uo0[mt][3], ue1[mt][0] + uo1[mt][1], ue1[mt][2] + uo1[mt][3]};
-    }
-    if (WK > 1) {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            *reinterpret_cast<f32x4*>(&red[((wave * MT + mt) * 128 + lane) * 4]) = ag[mt];
-            *reinterpret_cast<f32x4*>(&red[((wave * MT + mt) * 128 + 64 + lane) * 4]) = au[mt];
-        }
-        __syncthreads();
-        if (wave != 0) return;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            ag[mt] = au[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int w = 0; w < WK; ++w) {
-                const f32x4 vg = *reinterpret_cast<const f32x4*>(&red[((w * MT + mt) * 128 + lane) * 4]);
-                const f32x4 vu = *reinterpret_cast<const f32x4*>(&red[((w * MT + mt) * 128 + 64 + lane) * 4]);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    ag[mt][r] += vg[r];
-                    au[mt][r] += vu[r];
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt) {
-        const int m = m_base + mt * 16 + j;
-        if (m >= M) continue;
-#pragma unroll
-        for (int h2 = 0; h2 < 2; ++h2) {
-            const int n = n0 + h2 * 8 + 2 * g;
-            float hv[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const float gv = round_bf16(ag[mt][2 * h2 + q]), uv = round_bf16(au[mt][2 * h2 + q]);
-                hv[q] = round_bf16(gv / (1.0f + expf(-gv))) * uv;
-            }
-            bf16_t* dst = out + (size_t)m * inter + n;
-            if (n + 1 < inter && (inter & 1) == 0) *reinterpret_cast<uint32_t*>(dst) = f32x2_to_bf16x2(hv[0], hv[1]);
-            else {
-                if (n < inter) dst[0] = f32_to_bf16(hv[0]);
-                if (n + 1 < inter) dst[1] = f32_to_bf16(hv[1]);
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------- route + align in one launch
 // moe_align_block_size needs every token's ids, and the routing launch has one workgroup per token:
@@ -821,65 +616,6 @@ __global__ __launch_bounds__(1024) void gate_route_align_wg_softmax_kernel(
 
 }  // namespace chitu
 
-extern "C" int chitu_hip_bf16_gemm(const void* x_bf16, const void* w_bf16, void* out, int out_dtype,
-                                   int64_t M, int64_t N, int64_t K, int32_t num_splits,
-                                   float* partials, void* stream) {
-    using namespace chitu;
-    CHITU_REQUIRE(x_bf16 && w_bf16 && M >= 0 && N >= 1 && K >= 64 && N < (1 << 30) && K < (1 << 30));
-    CHITU_REQUIRE(num_splits >= 1 && num_splits <= 64);
-    CHITU_REQUIRE(num_splits > 1 ? partials != nullptr : (out != nullptr && out_dtype >= 0 && out_dtype <= 2));
-    if (K % 64 != 0) return CHITU_ERR_UNSUPPORTED;
-    if (M == 0) return CHITU_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int KB = (int)(K / 64);
-    const int tiles = (int)((N + 15) / 16);
-    if (num_splits > KB) return CHITU_ERR_BAD_ARG;
-    if ((M >= 256 || (M >= 128 && N >= 1024)) && K < (1 << 23) && debug_option(kOptBf16GemmTiled) != 0) {  // (32-bit byte offsets inside a tile)
-        // prefill-sized M: a GEMM, not a weight stream (bf16_gemm_tiled.hip); a 128-row prompt against the 256-row router
-        // matrix would be two workgroups -- that one stays with the split-K stream.  num_splits > 1: the K range cut over
-        // that many workgroups per tile, fp32 planes left in `partials` (the router of a long prompt: few tiles, long K)
-        launch_bf16_gemm_tiled((const bf16_t*)x_bf16, (const bf16_t*)w_bf16, out, out_dtype, M, N, K, num_splits, partials, st);
-        CHITU_RETURN_LAUNCH_STATUS();
-    }
-    const int S = num_splits;
-    int WK = 8;
-    while (WK > 1 && (WK * S > KB || (int64_t)tiles * S * WK > 4096)) WK >>= 1;
-    debug_override(kOptBf16GemmWK, WK);
-    while (WK > 1 && WK * S > KB) WK >>= 1;
-    const dim3 grid((unsigned)tiles, (unsigned)S);
-#define LAUNCH(MT, WKV)                                                                            \
-    hipLaunchKernelGGL((bf16_gemm_kernel<MT, WKV>), grid, dim3(64 * WKV), 0, st, (const bf16_t*)x_bf16, \
-                       (const bf16_t*)w_bf16, out, out_dtype, partials, (int)M, (int)N, (int)K, S, mbase)
-#define LAUNCH_WK(MT)                      \
-    switch (WK) {                          \
-        case 8: LAUNCH(MT, 8); break;      \
-        case 4: LAUNCH(MT, 4); break;      \
-        case 2: LAUNCH(MT, 2); break;      \
-        default: LAUNCH(MT, 1); break;     \
-    }
-    const int per_wave = KB / (WK * S);
-    for (int64_t mb = 0; mb < M; mb += 32) {
-        const int mbase = (int)mb;
-        if (M - mb <= 16) {
-            // the 8-deep ring (the wave's whole K range in one round trip) for grids of at most one workgroup per CU: its
-            // register count admits one 8-wave workgroup per CU, so a larger grid would run in rounds (Llama-3-8B's qkv
-            // projection, 384 workgroups; see bf16_norm_gemm.hip).  Option 11: 0 never, 1 always, -1 this heuristic.
-            const int deep_opt = debug_option(kOptBf16GemmDeep);
-            if (WK == 8 && per_wave > 4 && per_wave <= 8 && (deep_opt < 0 ? (int64_t)tiles * S <= 256 : deep_opt != 0))
-                hipLaunchKernelGGL((bf16_gemm_kernel<1, 8, true>), grid, dim3(512), 0, st, (const bf16_t*)x_bf16,
-                                   (const bf16_t*)w_bf16, out, out_dtype, partials, (int)M, (int)N, (int)K, S, mbase);
-            else
-                LAUNCH_WK(1)
-        } else {
-            LAUNCH_WK(2)
-        }
-    }
-#undef LAUNCH_WK
-#undef LAUNCH
-    // num_splits > 1: partials [S][M][N] are left for the consumer (chitu_hip_gate_route) to sum.
-    CHITU_RETURN_LAUNCH_STATUS();
-}
-
 static int gate_route_launch(const void* logits, int32_t num_partials, int64_t tokens, int32_t num_experts,
                              const void* bias_bf16, int32_t n_groups, int32_t topk_groups, int32_t topk,
                              int32_t score_func, float route_scale, void* out_weights_bf16, int64_t* out_ids,
@@ -1011,39 +747,6 @@ extern "C" int chitu_hip_gate_route_align(const void* logits, int32_t num_partia
     return gate_route_launch(logits, num_partials, tokens, num_experts, bias_bf16, n_groups, topk_groups, topk,
                              score_func, route_scale, out_weights_bf16, out_ids, out_stride, extra_expert_id,
                              extra_weight, extra_count, al, stream);
-}
-
-extern "C" int chitu_hip_bf16_gemm_silu(const void* x_bf16, const void* w13_bf16, void* out_bf16, int64_t M,
-                                        int64_t inter, int64_t K, void* stream) {
-    using namespace chitu;
-    CHITU_REQUIRE(x_bf16 && w13_bf16 && out_bf16 && M >= 0 && inter >= 1 && K >= 64 && inter < (1 << 29) && K < (1 << 30));
-    if (K % 64 != 0) return CHITU_ERR_UNSUPPORTED;
-    if (M == 0) return CHITU_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int KB = (int)(K / 64);
-    const int tiles = (int)((inter + 15) / 16);
-    int WK = 8;
-    while (WK > 1 && (WK > KB || (int64_t)tiles * WK > 4096)) WK >>= 1;
-    debug_override(kOptBf16SiluWK, WK);
-    while (WK > 1 && WK > KB) WK >>= 1;
-    const dim3 grid((unsigned)tiles);
-#define LAUNCHS(MT, WKV)                                                                                        \
-    hipLaunchKernelGGL((bf16_gemm_silu_kernel<MT, WKV>), grid, dim3(64 * WKV), 0, st, (const bf16_t*)x_bf16,    \
-                       (const bf16_t*)w13_bf16, (bf16_t*)out_bf16, (int)M, (int)inter, (int)K, mbase)
-#define LAUNCHS_WK(MT)                   \
-    switch (WK) {                        \
-        case 8: LAUNCHS(MT, 8); break;   \
-        case 4: LAUNCHS(MT, 4); break;   \
-        case 2: LAUNCHS(MT, 2); break;   \
-        default: LAUNCHS(MT, 1); break;  \
-    }
-    for (int64_t mb = 0; mb < M; mb += 32) {
-        const int mbase = (int)mb;
-        if (M - mb <= 16) { LAUNCHS_WK(1) } else { LAUNCHS_WK(2) }
-    }
-#undef LAUNCHS_WK
-#undef LAUNCHS
-    CHITU_RETURN_LAUNCH_STATUS();
 }
 
 CHITU_PROBE_READER(gate)

@@ -1,4 +1,4 @@
-// Pieces shared by the weight-streaming GEMM kernels (fp8_gemm.hip, gate.hip).
+// Pieces shared by the weight-streaming GEMM kernels (fp8_gemm.hip, stream_gemm.h and its users).
 #pragma once
 #include "common.h"
 
@@ -145,21 +145,48 @@ __device__ __forceinline__ f32x4 w8a8_block_dot(const W8Frag& f, const i32x4& x0
 // output column of accumulator element e (0..3) for lane group g, tile base n0
 __device__ __forceinline__ int w8_out_col(int n0, int g, int e) { return n0 + (e >> 1) * 8 + 2 * g + (e & 1); }
 
+// Per-column scale of an epilogue: cols() gives a lane the factors of its four accumulator elements (w8_out_col).
+// NoScale: none (the factor 1.0f folds away at compile time).  RowScale: one fp32 per weight row = output column,
+// v * s before the single rounding; shifted(n) is the scale vector of the rows n further down.
+struct NoScale {
+    struct Cols {
+        __device__ __forceinline__ constexpr float operator[](int) const { return 1.0f; }
+    };
+    __device__ __forceinline__ Cols cols(int, int, int) const { return Cols{}; }
+    __device__ __forceinline__ NoScale shifted(int) const { return NoScale{}; }
+};
+struct RowScale {
+    const float* s;
+    struct Cols {
+        float c[4];
+        __device__ __forceinline__ float operator[](int r) const { return c[r]; }
+    };
+    __device__ __forceinline__ Cols cols(int n0, int g, int N) const {
+        Cols k;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) k.c[r] = s[min(w8_out_col(n0, g, r), N - 1)];
+        return k;
+    }
+    __device__ __forceinline__ RowScale shifted(int n) const { return RowScale{s + n}; }
+};
+
 // Epilogue for the full-line layout: K-split reduce over the workgroup's waves (LDS, fixed order),
-// then per token two 2-column stores (columns 2g,2g+1 and 8+2g,8+2g+1 of the tile).
-template <int MT, int WK>
+// then per token two 2-column stores (columns 2g,2g+1 and 8+2g,8+2g+1 of the tile), scaled per column.
+template <int MT, int WK, class Scale = NoScale>
 __device__ __forceinline__ void gemm_epilogue_v2(f32x4 (&acc)[MT], float* red, void* out, int out_dt,
-                                                 float* partial, int M, int N, int S, int m_base, int n0) {
+                                                 float* partial, int M, int N, int S, int m_base, int n0,
+                                                 Scale scale = Scale{}) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: SGPR index math
     const int j = lane & 15, g = lane >> 4;
+    const auto sc = scale.cols(n0, g, N);
     auto store = [&](int mt, const f32x4& v) {
         const int m = m_base + mt * 16 + j;
         if (m >= M) return;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const int n = n0 + h * 8 + 2 * g;
-            const float a = v[2 * h], b = v[2 * h + 1];
+            const float a = v[2 * h] * sc[2 * h], b = v[2 * h + 1] * sc[2 * h + 1];
             if (S > 1) {
                 float* dst = partial + ((size_t)blockIdx.y * M + m) * N + n;
                 if (n < N) dst[0] = a;

@@ -9,7 +9,7 @@ Per layer and step, 7 launches: add+RMSNorm, wqkv GEMM, [RoPE(q, k) + append K, 
 (+ merge when the KV range is split), wo GEMM, add+RMSNorm, [w13 GEMM + SiluAndMul], w2 GEMM -- 4 at batch 1-2,
 where both add+RMSNorm steps run as the prologue of the GEMM behind them and RoPE + the K / V append as the
 epilogue of the qkv projection (bf16_norm_gemm.hip).
-All GEMMs are the weight-streaming skinny bf16 kernel (gate.hip); the whole step replays as one hipGraph.
+All GEMMs are the weight-streaming skinny bf16 kernel (bf16_gemm.hip); the whole step replays as one hipGraph.
 """
 
 import os

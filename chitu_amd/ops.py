@@ -1208,7 +1208,7 @@ def absorb_uv_quant_fp8(x, w, scale, scale_offset, scale_stride_h, scale_stride_
 def w8a16_tiled(M: int, n_rows: int, K: int) -> bool:
     """True where a W8A16 linear over `n_rows` weight rows takes the widen + tiled-GEMM + scale_round form: prefill-sized M,
     where the streaming kernel would read the weights once per 32 rows.  Started at chitu_hip_bf16_gemm's own rule
-    (csrc/gate.hip: M >= 256, or M >= 128 with >= 1024 rows) and moved by measurement (tools/w8a16_ab.py --sweep,
+    (csrc/bf16_gemm.hip: M >= 256, or M >= 128 with >= 1024 rows) and moved by measurement (tools/w8a16_ab.py --sweep,
     profiles/w8a16_ab.txt): at 128 tokens the widen launch still costs more than it saves on 4096-row matrices (tiled / stream
     1.09 - 1.19) and wins from 6144 rows on (0.61 - 0.68); at 192 tokens it wins everywhere (0.48 - 0.81).  Every M this
     returns True for lies inside the bf16 rule, so the GEMM over the widened weights is the compute-shaped one."""

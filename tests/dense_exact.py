@@ -396,7 +396,7 @@ F_TILED = [(m, n, k, s, tm, dt) for i, (((m, n), k), tm) in enumerate(itertools.
     for s, dt in [(1, OUT3[i % 3])]] + [
     (m, n, k, s, tm, "f32") for (m, n), (k, s), tm in itertools.product(
         [(257, 264), (300, 8)], [(320, 3), (320, 4), (1024, 3), (1024, 4)], [64, 128])]
-G_M = [1, 16, 17, 33, 255]
+G_M = [1, 16, 17, 33, 255, 32]   # 32 (last: the cases before it keep their shapes): one full two-tile launch, no row guarded
 G_CASES = [(m, [8, 136, 1000][i % 3], fits[(i + i // 3) % len(fits)], wk) for i, (m, wk) in enumerate(itertools.product(G_M, WKS))
            for fits in [[k for k in [64, 512, 2560] if k // 64 >= wk]]]                    # (M, inter, K, wk), launched WK = wk
 H_CASES = [(m, n, k, OUT3[(i + i // 6) % 3]) for i, (m, (n, k)) in enumerate(itertools.product(

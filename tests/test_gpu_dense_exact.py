@@ -40,7 +40,7 @@ computed values or move a store inside the guarded buffer) and what caught them 
     non-zero K stride (16 of 24) and ops.absorb_bmm_fp8 of section K; the w_uk stride set (K stride 0) rightly not.
   - fp8_gemm.hip, splitk_reduce_kernel: `s < S - 1`: all eight cases of section D, fp8 and soft, in the run with the full
     workspace ("workspace 236096 B (S=7) out f32: 8431 of 8432 elements differ"); nothing else reaches that kernel.
-  - gate.hip, bf16_gemm_kernel: `kb1 - 1` in wave 0 where it has more than one block: 37 cases of section F (streaming, DEEP
+  - bf16_gemm_kernel (then in gate.hip, now stream_gemm.h through bf16_gemm.hip): `kb1 - 1` in wave 0 where it has more than one block: 37 cases of section F (streaming, DEEP
     ring, split-K planes, and the tiled shapes streamed with bf16_gemm_tiled = 0).
   - w8a8_int8.hip: the channel scale of n + 1 for n: all five M of section J, "1555 of 1600 elements differ ... in 40 rows;
     worst row 0 (39 elements)" (the last channel reads its own scale).

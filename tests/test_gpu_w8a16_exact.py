@@ -133,6 +133,33 @@ def test_linear_entry_other_output_types(out_dtype):
         print(f"W8A16EXACT linear {out_dtype} M={M} N={N} K={K}: ok, {got.numel()} elements")
 
 
+@pytest.mark.parametrize("M,N,K", [(17, 24, 192), (33, 40, 512)])
+def test_int8_stream_equals_bf16_stream_over_the_widened_weights(M, N, K):
+    """The two line policies of stream_gemm.h against each other: with every scale 1.0 the int8 launch must equal the bf16
+    launch over ops.w8a16_widen(q), torch.equal -- the plain pair into fp32 (both accumulators are exact integers below 2^24,
+    wr.acc_int's own assertion), the SiLU pair into bf16 (the same device chain on the same exact accumulators)."""
+    from chitu_amd import ops
+    from chitu_amd._lib import check, i32, i64, ptr, stream_ptr
+
+    lib = _abi().lib()
+    for silu in (False, True):
+        rows = 2 * N if silu else N
+        x, q = wr.make_x(M, K, 70 + M), wr.make_q(rows, K, 80 + M)
+        wr.acc_int(x, q)
+        ones = torch.ones(rows, dtype=torch.float32)
+        xd, wide = x.cuda(), ops.w8a16_widen(q.cuda())
+        got = _run_stream("silu" if silu else "linear", x, q, ones, M, N, K, torch.bfloat16 if silu else torch.float32)
+        ref = torch.full((M, N), float("nan"), dtype=got.dtype, device="cuda")
+        if silu:
+            rc = lib.chitu_hip_bf16_gemm_silu(ptr(xd), ptr(wide), ptr(ref), i64(M), i64(N), i64(K), stream_ptr())
+        else:
+            rc = lib.chitu_hip_bf16_gemm(ptr(xd), ptr(wide), ptr(ref), i32(2), i64(M), i64(N), i64(K), i32(1), ptr(None), stream_ptr())
+        check(rc, "chitu_hip_bf16_gemm" + ("_silu" if silu else ""))
+        torch.cuda.synchronize()
+        assert not bool(torch.isnan(got.float()).any()) and torch.equal(got, ref.cpu()), (silu, M, N, K)
+        print(f"W8A16EXACT int8 == bf16 {'silu' if silu else 'linear'} M={M} N={N} K={K}: ok, {got.numel()} elements")
+
+
 @pytest.mark.parametrize("kind", ["pow2", "quantiser"])
 def test_prefill_sized_case_through_the_tiled_form(kind):
     """M = 256: widen (exact) + the tiled bf16 GEMM into fp32 + scale_round obey the same contract, so: bit-exact."""
