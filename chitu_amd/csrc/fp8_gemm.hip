@@ -18,24 +18,9 @@
 // kernel): deterministic, no atomics.
 #include "common.h"
 #include "gemm_common.h"
-// Profiling aid, compile-time only: a probe build (hipcc -DCHITU_GEMM_PHASE_MASK=<bits>) drops parts of fp8_gemm_kernel
-// (1: activation loads, 2: MFMAs, 4: activation-scale loads, 8: weight loads) to price them; such a build computes
-// garbage and is never shipped.  16: address the activations as if they were laid out tile-major ([K/16][16 tokens][16 B],
-// scales [K/128][16 tokens]) -- timing only.
-#ifndef CHITU_GEMM_PHASE_MASK
-#define CHITU_GEMM_PHASE_MASK 0
-#endif
+#include "gemm_plan.h"
 
 namespace chitu {
-
-typedef long mfma_ab_t;  // 8 fp8
-
-__device__ __forceinline__ mfma_ab_t pack_lo(const i32x4& v) {
-    return (long)(((unsigned long long)(uint32_t)v[1] << 32) | (uint32_t)v[0]);
-}
-__device__ __forceinline__ mfma_ab_t pack_hi(const i32x4& v) {
-    return (long)(((unsigned long long)(uint32_t)v[3] << 32) | (uint32_t)v[2]);
-}
 
 template <int MT>
 struct GemmStage {
@@ -82,9 +67,6 @@ __global__ __launch_bounds__(64 * WK) void fp8_gemm_kernel(
         if (TM) {
             xp[mt] = X + (size_t)(m >> 4) * 16 * K + (size_t)(g * 16 + (m & 15)) * 16;
             xsp[mt] = XS + (size_t)(m >> 4) * KB * 16 + (m & 15);
-        } else if (CHITU_GEMM_PHASE_MASK & 16) {
-            xp[mt] = X + (size_t)(g * 16 + (m & 15)) * 16;
-            xsp[mt] = XS + (m & 15);
         }
     }
 
@@ -92,38 +74,28 @@ __global__ __launch_bounds__(64 * WK) void fp8_gemm_kernel(
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) acc[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    constexpr int dbg = CHITU_GEMM_PHASE_MASK;  // 0 in every shipped build (see the macro)
     auto load = [&](GemmStage<MT>& st, int kb) {
         const int off = kb << 7;
-        if (!(dbg & 8)) {
-            st.w.w[0] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp0 + off));
-            st.w.w[1] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp1 + off));
-        } else {
-            st.w.w[0] = st.w.w[1] = i32x4{kb, lane, 3, 4};
-        }
+        (void)lane;  // stays in the closure: without it the lane-offset arithmetic of every instantiation compiles differently
+        st.w.w[0] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp0 + off));
+        st.w.w[1] = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp1 + off));
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            if (TM || (dbg & 16)) {  // chunk c = kb*8 + g (+4): 16 tokens x 16 B = 256 B per chunk
+            if (TM) {  // chunk c = kb*8 + g (+4): 16 tokens x 16 B = 256 B per chunk
                 st.x[mt][0] = *reinterpret_cast<const i32x4*>(xp[mt] + (size_t)kb * 2048);
                 st.x[mt][1] = *reinterpret_cast<const i32x4*>(xp[mt] + (size_t)kb * 2048 + 1024);
-            } else if (!(dbg & 1)) {
+            } else {
                 st.x[mt][0] = *reinterpret_cast<const i32x4*>(xp[mt] + off);
                 st.x[mt][1] = *reinterpret_cast<const i32x4*>(xp[mt] + off + 64);
-            } else {
-                st.x[mt][0] = st.x[mt][1] = i32x4{kb, lane, 1, 2};
             }
-            st.xs[mt] = (dbg & 4) ? 1.0f : (TM || (dbg & 16)) ? xsp[mt][kb * 16] : xsp[mt][kb];
+            st.xs[mt] = TM ? xsp[mt][kb * 16] : xsp[mt][kb];
         }
         st.ws = wsp[kb];
     };
     auto compute = [&](const GemmStage<MT>& st) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            f32x4 blk;
-            if (!(dbg & 2)) blk = w8a8_block_dot(st.w, st.x[mt][0], st.x[mt][1]);
-            else
-                blk = f32x4{__int_as_float(st.w.w[0][0] ^ st.x[mt][0][0]), __int_as_float(st.w.w[0][1] ^ st.x[mt][1][1]),
-                            __int_as_float(st.w.w[1][2] ^ st.x[mt][0][2]), __int_as_float(st.w.w[1][3] ^ st.x[mt][1][3])};
+            const f32x4 blk = w8a8_block_dot(st.w, st.x[mt][0], st.x[mt][1]);
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[mt][r] += (blk[r] * st.xs[mt]) * st.ws;
         }
@@ -132,6 +104,7 @@ __global__ __launch_bounds__(64 * WK) void fp8_gemm_kernel(
     // D-deep register ring: D K-blocks (2 KB of weights each) in flight per wave while one is consumed.
     // DEEP (single token tile, 5-8 K blocks per wave): the wave's whole K range is requested at once,
     // one HBM round trip instead of two -- these launches are latency-, not bandwidth-bound.
+    // (stream_gemm.h::stream_ring, written out: through the call no instantiation keeps its machine code)
     constexpr int D = DEEP ? 8 : MT >= 4 ? 2 : 4;
     GemmStage<MT> ring[D];
 #pragma unroll
@@ -229,51 +202,65 @@ __global__ __launch_bounds__(64 * WK) void soft_fp8_gemm_kernel(
 // from this many token rows on, the W8A8 GEMM is tiled for compute (fp8_gemm_tiled.hip) instead of streamed per 64 rows
 constexpr int kTiledMinRows = 128;
 
-struct SplitPlan {
-    int WK, S;
-};
+// The W8A8 stream, one launch per 64-row pass: MT from the rows left and WK from the plan (stream_walk_m), row- or
+// tile-major activations, and the DEEP ring where `deep` (gemm_plan.h::fp8_deep) holds on a single-tile pass of 8 waves --
+// the only instantiations of DEEP.  partial: the S > 1 planes.
+static void launch_fp8_stream(SplitPlan plan, bool deep, bool tile_major, const void* a_fp8, const float* a_scale,
+                              const void* b_fp8, const float* b_scale, void* out, int out_dt, float* partial, int64_t M,
+                              int64_t N, int64_t K, hipStream_t st) {
+    const dim3 grid((unsigned)((N + 15) / 16), (unsigned)plan.S);
+    auto launch = [&](int m_base, auto mt, auto wk, auto dp, auto tm) {
+        constexpr int MT = decltype(mt)::value, WK = decltype(wk)::value;
+        hipLaunchKernelGGL((fp8_gemm_kernel<MT, WK, decltype(dp)::value, decltype(tm)::value>), grid, dim3(64 * WK), 0, st,
+                           (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, out, out_dt, partial, (int)M, (int)N,
+                           (int)K, plan.S, m_base);
+    };
+    // (an option value that is none of 1, 2, 4 launches 8 waves, as it always has)
+    const int waves = plan.WK == 1 || plan.WK == 2 || plan.WK == 4 ? plan.WK : 8;
+    stream_walk_m<64>(M, waves, [&](int m_base, auto mt, auto wk) {
+        auto with_tm = [&](auto dp) {
+            if (tile_major) launch(m_base, mt, wk, dp, std::true_type{});
+            else launch(m_base, mt, wk, dp, std::false_type{});
+        };
+        if constexpr (decltype(mt)::value == 1 && decltype(wk)::value == 8) {
+            if (deep) return with_tm(std::true_type{});
+        }
+        with_tm(std::false_type{});
+    });
+}
 
-static SplitPlan plan_split(int N, int K) {
-    const int tiles = (N + 15) / 16;
-    const int KB = (K + 127) / 128;
-    int T = (1536 + tiles - 1) / tiles;
-    if (T > KB) T = KB;
-    if (T < 1) T = 1;
-    int WK = 1;
-    while (WK * 2 <= T && WK < 8) WK *= 2;
-    // A cross-workgroup split costs a second (reduce) launch: measured ~5 us inside the decode
-    // graph, more than the few us it saves on <= 16 MB of weights.  Only use it when N alone
-    // leaves most of the chip idle AND the matrix is big enough to matter.
-    int S = 1;
-    if (tiles * WK < 256 && (int64_t)N * K >= (int64_t)(24 << 20)) {
-        S = (T + WK - 1) / WK;
-        if (S > 8) S = 8;
-        if (S * WK > KB) S = KB / WK > 0 ? KB / WK : 1;
-    }
-    return {WK, S};
+// out = the sum of the S planes in plane order (the second launch of an in-library split)
+static void launch_splitk_reduce(const float* partial, void* out, int out_dt, int S, int64_t MN, hipStream_t st) {
+    int blocks = (int)((MN / 4 + 255) / 256);
+    if (blocks < 1) blocks = 1;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, partial, out, out_dt, S, MN);
 }
 
 }  // namespace chitu
 
-#define DISPATCH_WK(KERNEL, MT, ...)                                                          \
-    switch (plan.WK) {                                                                        \
-        case 1: hipLaunchKernelGGL((KERNEL<MT, 1>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-        case 2: hipLaunchKernelGGL((KERNEL<MT, 2>), grid, dim3(128), 0, st, __VA_ARGS__); break;  \
-        case 4: hipLaunchKernelGGL((KERNEL<MT, 4>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL((KERNEL<MT, 8>), grid, dim3(512), 0, st, __VA_ARGS__); break; \
-    }
-// the same for tile-major activations (fp8_gemm_kernel<MT, WK, DEEP, TM = true>)
-#define DISPATCH_WK_TM(MT, ...)                                                                                   \
-    switch (plan.WK) {                                                                                            \
-        case 1: hipLaunchKernelGGL((fp8_gemm_kernel<MT, 1, false, true>), grid, dim3(64), 0, st, __VA_ARGS__); break;   \
-        case 2: hipLaunchKernelGGL((fp8_gemm_kernel<MT, 2, false, true>), grid, dim3(128), 0, st, __VA_ARGS__); break;  \
-        case 4: hipLaunchKernelGGL((fp8_gemm_kernel<MT, 4, false, true>), grid, dim3(256), 0, st, __VA_ARGS__); break;  \
-        default: hipLaunchKernelGGL((fp8_gemm_kernel<MT, 8, false, true>), grid, dim3(512), 0, st, __VA_ARGS__); break; \
-    }
-
 static int fp8_gemm_blockscale_launch(const void* a_fp8, const float* a_scale, const void* b_fp8, const float* b_scale,
                                       void* out, int out_dtype, int64_t M, int64_t N, int64_t K, void* workspace,
-                                      int64_t workspace_bytes, bool tile_major, void* stream);
+                                      int64_t workspace_bytes, bool tile_major, void* stream) {
+    using namespace chitu;
+    CHITU_REQUIRE(a_fp8 && a_scale && b_fp8 && b_scale && out);
+    CHITU_REQUIRE(M >= 0 && N >= 1 && K >= 128 && N < (1 << 30) && K < (1 << 30));
+    CHITU_REQUIRE(out_dtype >= 0 && out_dtype <= 2);
+    if (K % 128 != 0) return CHITU_ERR_UNSUPPORTED;  // act_quant's contract, ops.py:345-348
+    if (M == 0) return CHITU_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (!tile_major && M >= kTiledMinRows && K < (1 << 24) && M * (K / 128) < (1ll << 29) &&
+        debug_option(kOptFp8GemmTiled) != 0) {  // (32-bit byte offsets inside a 128-row tile, and of a row's scales: 4 M K/128 < 2^31)
+        // prefill-sized M: a GEMM, not a weight stream (fp8_gemm_tiled.hip)
+        launch_fp8_gemm_tiled((const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, out, out_dtype, M, N, K, st);
+        CHITU_RETURN_LAUNCH_STATUS();
+    }
+    const SplitPlan plan = fp8_stream_plan(M, N, K, workspace ? workspace_bytes : 0, debug_option(kOptFp8GemmWK));
+    launch_fp8_stream(plan, fp8_deep(plan, K, debug_option(kOptFp8GemmDeep)), tile_major, a_fp8, a_scale, b_fp8, b_scale, out,
+                      out_dtype, (float*)workspace, M, N, K, st);
+    if (plan.S > 1) launch_splitk_reduce((const float*)workspace, out, out_dtype, plan.S, M * N, st);
+    CHITU_RETURN_LAUNCH_STATUS();
+}
 
 extern "C" int chitu_hip_fp8_gemm_blockscale(const void* a_fp8, const float* a_scale,
                                              const void* b_fp8, const float* b_scale, void* out,
@@ -296,78 +283,6 @@ extern "C" int chitu_hip_fp8_gemm_blockscale_tm(const void* a_fp8, const float* 
                                       true, stream);
 }
 
-static int fp8_gemm_blockscale_launch(const void* a_fp8, const float* a_scale, const void* b_fp8, const float* b_scale,
-                                      void* out, int out_dtype, int64_t M, int64_t N, int64_t K, void* workspace,
-                                      int64_t workspace_bytes, bool tile_major, void* stream) {
-    using namespace chitu;
-    CHITU_REQUIRE(a_fp8 && a_scale && b_fp8 && b_scale && out);
-    CHITU_REQUIRE(M >= 0 && N >= 1 && K >= 128 && N < (1 << 30) && K < (1 << 30));
-    CHITU_REQUIRE(out_dtype >= 0 && out_dtype <= 2);
-    if (K % 128 != 0) return CHITU_ERR_UNSUPPORTED;  // act_quant's contract, ops.py:345-348
-    if (M == 0) return CHITU_OK;
-    hipStream_t st = (hipStream_t)stream;
-    if (!tile_major && M >= kTiledMinRows && K < (1 << 24) && M * (K / 128) < (1ll << 29) &&
-        debug_option(kOptFp8GemmTiled) != 0) {  // (32-bit byte offsets inside a 128-row tile, and of a row's scales: 4 M K/128 < 2^31)
-        // prefill-sized M: a GEMM, not a weight stream (fp8_gemm_tiled.hip)
-        launch_fp8_gemm_tiled((const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, out, out_dtype, M, N, K, st);
-        CHITU_RETURN_LAUNCH_STATUS();
-    }
-    SplitPlan plan = plan_split((int)N, (int)K);
-    if (plan.S > 1 && (!workspace || workspace_bytes < (int64_t)plan.S * M * N * 4)) plan.S = 1;
-    debug_override(kOptFp8GemmWK, plan.WK);
-    while (plan.WK > 1 && plan.WK * plan.S > (int)(K / 128)) plan.WK >>= 1;
-    const dim3 grid((unsigned)((N + 15) / 16), (unsigned)plan.S);
-    float* partial = (float*)workspace;
-    for (int64_t mb = 0; mb < M; mb += 64) {
-        const int rem = (int)(M - mb);
-        const int mbase = (int)mb;
-        if (tile_major) {
-            if (rem <= 16) {
-                const int per_wave = (int)(K / 128) / (plan.WK * plan.S);
-                if (plan.WK == 8 && per_wave > 4 && per_wave <= 8 && debug_option(kOptFp8GemmDeep) != 0)
-                    hipLaunchKernelGGL((fp8_gemm_kernel<1, 8, true, true>), grid, dim3(512), 0, st, (const fp8_t*)a_fp8, a_scale,
-                                       (const fp8_t*)b_fp8, b_scale, out, out_dtype, partial, (int)M, (int)N, (int)K,
-                                       plan.S, mbase);
-                else
-                    DISPATCH_WK_TM(1, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, out, out_dtype, partial,
-                                   (int)M, (int)N, (int)K, plan.S, mbase)
-            } else if (rem <= 32) {
-                DISPATCH_WK_TM(2, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, out, out_dtype, partial,
-                               (int)M, (int)N, (int)K, plan.S, mbase)
-            } else {
-                DISPATCH_WK_TM(4, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, out, out_dtype, partial,
-                               (int)M, (int)N, (int)K, plan.S, mbase)
-            }
-            continue;
-        }
-        if (rem <= 16) {
-            const int per_wave = (int)(K / 128) / (plan.WK * plan.S);
-            if (plan.WK == 8 && per_wave > 4 && per_wave <= 8 && debug_option(kOptFp8GemmDeep) != 0)
-                hipLaunchKernelGGL((fp8_gemm_kernel<1, 8, true>), grid, dim3(512), 0, st, (const fp8_t*)a_fp8, a_scale,
-                                   (const fp8_t*)b_fp8, b_scale, out, out_dtype, partial, (int)M, (int)N, (int)K,
-                                   plan.S, mbase);
-            else
-                DISPATCH_WK(fp8_gemm_kernel, 1, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale,
-                            out, out_dtype, partial, (int)M, (int)N, (int)K, plan.S, mbase)
-        } else if (rem <= 32) {
-            DISPATCH_WK(fp8_gemm_kernel, 2, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale,
-                        out, out_dtype, partial, (int)M, (int)N, (int)K, plan.S, mbase)
-        } else {
-            DISPATCH_WK(fp8_gemm_kernel, 4, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale,
-                        out, out_dtype, partial, (int)M, (int)N, (int)K, plan.S, mbase)
-        }
-    }
-    if (plan.S > 1) {
-        const int64_t MN = M * N;
-        int blocks = (int)((MN / 4 + 255) / 256);
-        if (blocks < 1) blocks = 1;
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, partial, out,
-                           out_dtype, plan.S, MN);
-    }
-    CHITU_RETURN_LAUNCH_STATUS();
-}
-
 // Split-K form for the few dense GEMMs whose N alone cannot fill the chip (wqkv_a: 132 tiles on 256 CUs): the K
 // range is cut over `num_splits` workgroups per tile and the fp32 partial planes [num_splits, M, N] are the
 // OUTPUT -- no reduce launch; the consumer (chitu_hip_mla_qkv_post with num_partials) sums the planes in order
@@ -379,27 +294,10 @@ extern "C" int chitu_hip_fp8_gemm_blockscale_partials(const void* a_fp8, const f
     CHITU_REQUIRE(a_fp8 && a_scale && b_fp8 && b_scale && partials);
     CHITU_REQUIRE(M >= 0 && N >= 1 && K >= 128 && N < (1 << 30) && K < (1 << 30));
     if (K % 128 != 0) return CHITU_ERR_UNSUPPORTED;
-    const int KB = (int)(K / 128);
-    CHITU_REQUIRE(num_splits >= 2 && num_splits <= 16 && num_splits <= KB);
+    CHITU_REQUIRE(num_splits >= 2 && num_splits <= 16 && num_splits <= (int)(K / 128));
     if (M == 0) return CHITU_OK;
-    hipStream_t st = (hipStream_t)stream;
-    SplitPlan plan{1, (int)num_splits};
-    while (plan.WK < 8 && plan.WK * 2 * plan.S <= KB) plan.WK *= 2;
-    const dim3 grid((unsigned)((N + 15) / 16), (unsigned)plan.S);
-    for (int64_t mb = 0; mb < M; mb += 64) {
-        const int rem = (int)(M - mb);
-        const int mbase = (int)mb;
-        if (rem <= 16) {
-            DISPATCH_WK(fp8_gemm_kernel, 1, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, nullptr, 2,
-                        partials, (int)M, (int)N, (int)K, plan.S, mbase)
-        } else if (rem <= 32) {
-            DISPATCH_WK(fp8_gemm_kernel, 2, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, nullptr, 2,
-                        partials, (int)M, (int)N, (int)K, plan.S, mbase)
-        } else {
-            DISPATCH_WK(fp8_gemm_kernel, 4, (const fp8_t*)a_fp8, a_scale, (const fp8_t*)b_fp8, b_scale, nullptr, 2,
-                        partials, (int)M, (int)N, (int)K, plan.S, mbase)
-        }
-    }
+    launch_fp8_stream(fp8_partials_plan(K, (int)num_splits), false, false, a_fp8, a_scale, b_fp8, b_scale, nullptr, 2, partials,
+                      M, N, K, (hipStream_t)stream);
     CHITU_RETURN_LAUNCH_STATUS();
 }
 
@@ -413,29 +311,15 @@ extern "C" int chitu_hip_soft_fp8_gemm(const void* a_bf16, const void* b_fp8, co
     if (K % 128 != 0) return CHITU_ERR_UNSUPPORTED;
     if (M == 0) return CHITU_OK;
     hipStream_t st = (hipStream_t)stream;
-    SplitPlan plan = plan_split((int)N, (int)K);
-    if (plan.S > 1 && (!workspace || workspace_bytes < (int64_t)plan.S * M * N * 4)) plan.S = 1;
+    const SplitPlan plan = fp8_plan_in_workspace(M, N, K, workspace ? workspace_bytes : 0);
     const dim3 grid((unsigned)((N + 15) / 16), (unsigned)plan.S);
-    float* partial = (float*)workspace;
-    for (int64_t mb = 0; mb < M; mb += 32) {
-        const int rem = (int)(M - mb);
-        const int mbase = (int)mb;
-        if (rem <= 16) {
-            DISPATCH_WK(soft_fp8_gemm_kernel, 1, (const bf16_t*)a_bf16, (const fp8_t*)b_fp8, b_scale, out,
-                        out_dtype, partial, (int)M, (int)N, (int)K, plan.S, mbase)
-        } else {
-            DISPATCH_WK(soft_fp8_gemm_kernel, 2, (const bf16_t*)a_bf16, (const fp8_t*)b_fp8, b_scale, out,
-                        out_dtype, partial, (int)M, (int)N, (int)K, plan.S, mbase)
-        }
-    }
-    if (plan.S > 1) {
-        const int64_t MN = M * N;
-        int blocks = (int)((MN / 4 + 255) / 256);
-        if (blocks < 1) blocks = 1;
-        if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, partial, out,
-                           out_dtype, plan.S, MN);
-    }
+    stream_walk_m<32>(M, plan.WK, [&](int m_base, auto mt, auto wk) {
+        constexpr int MT = decltype(mt)::value, WK = decltype(wk)::value;
+        hipLaunchKernelGGL((soft_fp8_gemm_kernel<MT, WK>), grid, dim3(64 * WK), 0, st, (const bf16_t*)a_bf16,
+                           (const fp8_t*)b_fp8, b_scale, out, out_dtype, (float*)workspace, (int)M, (int)N, (int)K, plan.S,
+                           m_base);
+    });
+    if (plan.S > 1) launch_splitk_reduce((const float*)workspace, out, out_dtype, plan.S, M * N, st);
     CHITU_RETURN_LAUNCH_STATUS();
 }
 

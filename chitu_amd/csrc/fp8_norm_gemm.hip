@@ -19,13 +19,14 @@
 // wave-order reduce as fp8_gemm_kernel (fp8_gemm.hip): the output is BIT-IDENTICAL to the two launches.
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_plan.h"
 #include "norm_common.h"
 
 namespace chitu {
 
 constexpr int kFp8NormMaxRows = 2;
 
-// WK: waves per workgroup = K split (fp8_gemm.hip's plan for the shape); MAXT: term registers (>= terms); MR: rows held.
+// WK: waves per workgroup = K split (gemm_plan.h::fp8_norm_gemm_wk); MAXT: term registers (>= terms); MR: rows held.
 template <int WK, int MAXT, int MR>
 __global__ __launch_bounds__(64 * WK) void fp8_gemm_add_norm_kernel(
     const bf16_t* x, int64_t x_stride, const bf16_t* add, int64_t add_stride, int terms, int64_t term_stride, bf16_t* sum_out,
@@ -59,7 +60,8 @@ __global__ __launch_bounds__(64 * WK) void fp8_gemm_add_norm_kernel(
     }
 #pragma unroll
     for (int i = 0; i < NCH; ++i) wr[i] = *reinterpret_cast<const i32x4*>(nw + min(tid + i * T, n_chunks - 1) * 8);
-    // ---- the wave's weight blocks (WK = 8: its whole K range when that is <= 8 blocks, one round trip)
+    // ---- the wave's weight blocks (WK = 8: its whole K range when that is <= 8 blocks, one round trip); the ring is
+    // stream_gemm.h::stream_ring cut in two -- filled here, ahead of the norm, and turned in the K loop below
     const fp8_t *wp0, *wp1;
     w8_lane_ptrs(W, n0, N, K, j, g, wp0, wp1);
     const float* wsp = WS + (size_t)(n0 >> 7) * KB;
@@ -165,20 +167,6 @@ __global__ __launch_bounds__(64 * WK) void fp8_gemm_add_norm_kernel(
     gemm_epilogue_v2<1, WK>(accv, red, out, out_dt, nullptr, M, N, 1, 0, n0);
 }
 
-// the K split chitu_hip_fp8_gemm_blockscale picks for this shape (fp8_gemm.hip::plan_split; kept in step so that the fused
-// and the unfused launches accumulate in the same order); 0 = a cross-workgroup split or < 4 waves: not served here
-static int fp8_norm_gemm_wk(int64_t N, int64_t K) {
-    const int tiles = (int)((N + 15) / 16), KB = (int)(K / 128);
-    int T = (1536 + tiles - 1) / tiles;
-    if (T > KB) T = KB;
-    if (T < 1) T = 1;
-    int WK = 1;
-    while (WK * 2 <= T && WK < 8) WK *= 2;
-    if (tiles * WK < 256 && N * K >= (int64_t)(24 << 20)) return 0;  // plan_split would cut K across workgroups
-    while (WK > 1 && WK > KB) WK >>= 1;
-    return WK >= 4 ? WK : 0;
-}
-
 }  // namespace chitu
 
 extern "C" int chitu_hip_fp8_gemm_add_norm(const void* x_bf16, int64_t x_row_stride, const void* add_bf16,
@@ -194,7 +182,7 @@ extern "C" int chitu_hip_fp8_gemm_add_norm(const void* x_bf16, int64_t x_row_str
     if (M == 0) return CHITU_OK;
     if (K % 128 != 0 || K > kNormWideThreads * 8 || add_terms > kNormMaxTerms) return CHITU_ERR_UNSUPPORTED;
     if (M > kFp8NormMaxRows || (M == 2 && add_terms != 1)) return CHITU_ERR_UNSUPPORTED;
-    const int WK = fp8_norm_gemm_wk(N, K);
+    const int WK = fp8_norm_gemm_wk(N, K);  // the unfused launch's K split: the same accumulation order
     if (WK == 0) return CHITU_ERR_UNSUPPORTED;
     const int tiles = (int)((N + 15) / 16);
     const size_t lds = (size_t)M * K + (size_t)M * (K / 128) * 4;

@@ -1,12 +1,16 @@
-// Pieces shared by the weight-streaming GEMM kernels (fp8_gemm.hip, stream_gemm.h and its users).
+// Device-side pieces shared by the weight-streaming GEMM kernels (fp8_gemm.hip, fp8_norm_gemm.hip, mla_q_proj.hip,
+// w8a8_int8.hip, stream_gemm.h and its users, the expert GEMMs): the two epilogues with their K-split reduce, the full-line
+// weight layout with its half-fold (fold_halves) and block dot, the per-block fold of the tiled GEMMs (fold_scaled).  The
+// launch rules of these kernels are gemm_plan.h.
 #pragma once
 #include "common.h"
 
 namespace chitu {
 
-// Epilogue shared by both kernels: K-split reduce across the workgroup's waves through LDS
-// in fixed wave order, then one token-tile per wave is written (bf16/f16/f32, or the fp32
-// partial slab of cross-workgroup split `blockIdx.y`).
+// Epilogue of the 64-byte row layout (soft_fp8_gemm_kernel): K-split reduce across the workgroup's waves through LDS in
+// fixed wave order, then one token-tile per wave is written, four adjacent columns per lane (bf16/f16/f32, or the fp32
+// partial slab of cross-workgroup split `blockIdx.y`).  The reduce stands written out here, in gemm_epilogue_v2 and in
+// w8a8_int8_gemm_kernel (int32): behind one function that takes the store, every kernel compiles differently.
 template <int MT, int WK>
 __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[MT], float* red, void* out, int out_dt,
                                               float* partial, int M, int N, int S, int m_base,
@@ -61,7 +65,6 @@ __device__ __forceinline__ void gemm_epilogue(f32x4 (&acc)[MT], float* red, void
         for (int mt = 0; mt < MT; ++mt) store(mt, acc[mt]);
     }
 }
-
 
 // ---- full-line ("pattern 2") FP8 weight tile -------------------------------------------------
 // Measured on MI355X (tools/probe_stream.hip): a wave-load that takes 64 B from each of 16 rows
@@ -118,6 +121,13 @@ __device__ __forceinline__ void fold_scaled(f32x4& acc, const f32x4& d, float a_
     acc = __builtin_elementwise_fma(t, f32x4{b_s, b_s, b_s, b_s}, acc);
 }
 
+// out rows {2g, 2g+1, 8+2g, 8+2g+1} of a tile from the even / odd half products of row groups 0 and 1 (f32x4 or i32x4;
+// by value: by reference the fused kernels of bf16_norm_gemm.hip compile differently)
+template <class V>
+__device__ __forceinline__ V fold_halves(V e0, V o0, V e1, V o1) {
+    return V{e0[0] + o0[1], e0[2] + o0[3], e1[0] + o1[1], e1[2] + o1[3]};
+}
+
 // lane's weight pointer for K block 0: W + row*K + ((j&1)*4 + g)*16, rows clamped to n_rows-1
 __device__ __forceinline__ void w8_lane_ptrs(const fp8_t* Wbase, int n0, int n_rows, int K, int j, int g,
                                              const fp8_t*& p0, const fp8_t*& p1) {
@@ -139,7 +149,7 @@ __device__ __forceinline__ f32x4 w8a8_block_dot(const W8Frag& f, const i32x4& x0
     o0 = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(frag_hi(f.w[0]), frag_hi(x1), o0, 0, 0, 0);
     e1 = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(frag_hi(f.w[1]), frag_hi(x0), e1, 0, 0, 0);
     o1 = __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(frag_hi(f.w[1]), frag_hi(x1), o1, 0, 0, 0);
-    return f32x4{e0[0] + o0[1], e0[2] + o0[3], e1[0] + o1[1], e1[2] + o1[3]};
+    return fold_halves(e0, o0, e1, o1);
 }
 
 // output column of accumulator element e (0..3) for lane group g, tile base n0
@@ -170,8 +180,8 @@ struct RowScale {
     __device__ __forceinline__ RowScale shifted(int n) const { return RowScale{s + n}; }
 };
 
-// Epilogue for the full-line layout: K-split reduce over the workgroup's waves (LDS, fixed order),
-// then per token two 2-column stores (columns 2g,2g+1 and 8+2g,8+2g+1 of the tile), scaled per column.
+// Epilogue for the full-line layout: K-split reduce over the workgroup's waves (LDS, fixed order), then per token two
+// 2-column stores (columns 2g,2g+1 and 8+2g,8+2g+1 of the tile), scaled per column.
 template <int MT, int WK, class Scale = NoScale>
 __device__ __forceinline__ void gemm_epilogue_v2(f32x4 (&acc)[MT], float* red, void* out, int out_dt,
                                                  float* partial, int M, int N, int S, int m_base, int n0,

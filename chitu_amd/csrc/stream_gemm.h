@@ -25,13 +25,9 @@
 
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_plan.h"  // the host side: stream_wk, stream_walk_m
 
 namespace chitu {
-
-// out rows {2g, 2g+1, 8+2g, 8+2g+1} of a tile from the even / odd half products of row groups 0 and 1
-__device__ __forceinline__ f32x4 fold_halves(f32x4 e0, f32x4 o0, f32x4 e1, f32x4 o1) {
-    return f32x4{e0[0] + o0[1], e0[2] + o0[3], e1[0] + o1[1], e1[2] + o1[3]};
-}
 
 // f(0), ..., f(N - 1) with the index as a std::integral_constant: a loop unrolled in the source
 template <int N, class F>
@@ -240,33 +236,6 @@ __device__ __forceinline__ void stream_gemm_silu(const bf16_t* __restrict__ X, c
         au[mt] = fold_halves(ln.e[2][mt], ln.o[2][mt], ln.e[3][mt], ln.o[3][mt]);
     }
     silu_reduce_store<MT, WK>(ag, au, red, out, M, inter, m_base, ln.n0, scale);
-}
-
-// ---------------------------------------------------------------- host side
-// K-split width: the widest power of two <= 8 that leaves every wave (of each of the S grid splits) a K step and the launch
-// at most 4096 waves.  Mirrored by chitu_amd.ops.w8a16_plan and tests/dense_exact.py::bf16_wk.
-static inline int stream_wk(int64_t tiles, int64_t steps, int64_t S = 1) {
-    int WK = 8;
-    while (WK > 1 && (WK * S > steps || tiles * S * WK > 4096)) WK >>= 1;
-    return WK;
-}
-
-// The M walk: 32-row launches, launch(m_base, MT, WK) with MT = 1 when at most 16 rows are left, else 2, and WK one of
-// 8, 4, 2, 1 -- both as std::integral_constant, for the kernel's template arguments.
-template <class F>
-static inline void stream_walk_m(int64_t M, int WK, F&& launch) {
-    auto with_wk = [&](int m_base, auto mt) {
-        switch (WK) {
-            case 8: launch(m_base, mt, std::integral_constant<int, 8>{}); break;
-            case 4: launch(m_base, mt, std::integral_constant<int, 4>{}); break;
-            case 2: launch(m_base, mt, std::integral_constant<int, 2>{}); break;
-            default: launch(m_base, mt, std::integral_constant<int, 1>{}); break;
-        }
-    };
-    for (int64_t mb = 0; mb < M; mb += 32) {
-        if (M - mb <= 16) with_wk((int)mb, std::integral_constant<int, 1>{});
-        else with_wk((int)mb, std::integral_constant<int, 2>{});
-    }
 }
 
 }  // namespace chitu

@@ -13,10 +13,9 @@
 // per 16 rows; no per-block scales, so the int32 accumulators run across the whole K range.
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_plan.h"
 
 namespace chitu {
-
-typedef int i32x4v __attribute__((ext_vector_type(4)));
 
 struct bf16_in { uint16_t v; };
 struct f16_in { uint16_t v; };
@@ -56,9 +55,9 @@ __global__ __launch_bounds__(256) void quant_act_int8_vec_kernel(const uint16_t*
     const int row = blockIdx.x, tid = threadIdx.x;
     const int n_chunks = K >> 3;
     const uint16_t* xr = x + (int64_t)row * K;
-    i32x4v raw[CH];
+    i32x4 raw[CH];
 #pragma unroll
-    for (int c = 0; c < CH; ++c) raw[c] = *reinterpret_cast<const i32x4v*>(xr + (size_t)min(tid + c * 256, n_chunks - 1) * 8);
+    for (int c = 0; c < CH; ++c) raw[c] = *reinterpret_cast<const i32x4*>(xr + (size_t)min(tid + c * 256, n_chunks - 1) * 8);
     float v[CH][8];
     float amax = 0.f;
 #pragma unroll
@@ -117,30 +116,30 @@ __global__ __launch_bounds__(64 * WK) void w8a8_int8_gemm_kernel(
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) xp[mt] = X + (size_t)min(m_base + mt * 16 + j, M - 1) * K + g * 16;
 
-    i32x4v e0[MT], o0[MT], e1[MT], o1[MT];
+    i32x4 e0[MT], o0[MT], e1[MT], o1[MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) e0[mt] = o0[mt] = e1[mt] = o1[mt] = i32x4v{0, 0, 0, 0};
+    for (int mt = 0; mt < MT; ++mt) e0[mt] = o0[mt] = e1[mt] = o1[mt] = i32x4{0, 0, 0, 0};
 
     for (int kb = kb0; kb < kb1; ++kb) {
         const int off = kb << 7;
-        const i32x4v w0 = __builtin_nontemporal_load(reinterpret_cast<const i32x4v*>(wp0 + off));
-        const i32x4v w1 = __builtin_nontemporal_load(reinterpret_cast<const i32x4v*>(wp1 + off));
+        const i32x4 w0 = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp0 + off));
+        const i32x4 w1 = __builtin_nontemporal_load(reinterpret_cast<const i32x4*>(wp1 + off));
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
-            const i32x4v x0 = *reinterpret_cast<const i32x4v*>(xp[mt] + off);
-            const i32x4v x1 = *reinterpret_cast<const i32x4v*>(xp[mt] + off + 64);
+            const i32x4 x0 = *reinterpret_cast<const i32x4*>(xp[mt] + off);
+            const i32x4 x1 = *reinterpret_cast<const i32x4*>(xp[mt] + off + 64);
             e0[mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, x0, e0[mt], 0, 0, 0);
             o0[mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w0, x1, o0[mt], 0, 0, 0);
             e1[mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, x0, e1[mt], 0, 0, 0);
             o1[mt] = __builtin_amdgcn_mfma_i32_16x16x64_i8(w1, x1, o1[mt], 0, 0, 0);
         }
     }
-    // in-lane combine of the even/odd half-row products (gemm_common.h), exact in int32
-    i32x4v acc[MT];
+    // in-lane combine of the even/odd half-row products (gemm_common.h::fold_halves, in int32: exact)
+    i32x4 acc[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
-        acc[mt] = i32x4v{e0[mt][0] + o0[mt][1], e0[mt][2] + o0[mt][3], e1[mt][0] + o1[mt][1], e1[mt][2] + o1[mt][3]};
-    auto store = [&](int mt, const i32x4v& v) {
+        acc[mt] = i32x4{e0[mt][0] + o0[mt][1], e0[mt][2] + o0[mt][3], e1[mt][0] + o1[mt][1], e1[mt][2] + o1[mt][3]};
+    auto store = [&](int mt, const i32x4& v) {
         const int m = m_base + mt * 16 + j;
         if (m >= M) return;
         const float sa = XS[m];
@@ -157,13 +156,13 @@ __global__ __launch_bounds__(64 * WK) void w8a8_int8_gemm_kernel(
     if (WK > 1) {
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
-            *reinterpret_cast<i32x4v*>(&red[((wave * MT + mt) * 64 + lane) * 4]) = acc[mt];
+            *reinterpret_cast<i32x4*>(&red[((wave * MT + mt) * 64 + lane) * 4]) = acc[mt];
         __syncthreads();
         for (int mt = wave; mt < MT; mt += WK) {
-            i32x4v sum = i32x4v{0, 0, 0, 0};
+            i32x4 sum = i32x4{0, 0, 0, 0};
 #pragma unroll
             for (int w = 0; w < WK; ++w) {
-                const i32x4v v = *reinterpret_cast<const i32x4v*>(&red[((w * MT + mt) * 64 + lane) * 4]);
+                const i32x4 v = *reinterpret_cast<const i32x4*>(&red[((w * MT + mt) * 64 + lane) * 4]);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) sum[r] += v[r];
             }
@@ -210,27 +209,11 @@ extern "C" int chitu_hip_w8a8_int8_gemm(const void* a_int8, const float* a_scale
     if (K % 128 != 0) return CHITU_ERR_UNSUPPORTED;
     if (M == 0) return CHITU_OK;
     hipStream_t st = (hipStream_t)stream;
-    const int tiles = (int)((N + 15) / 16);
-    const int KB = (int)(K / 128);
-    int WK = tiles >= 1024 ? 2 : tiles >= 384 ? 4 : 8;
-    while (WK > 1 && WK > KB) WK >>= 1;
-    const dim3 grid((unsigned)tiles);
-#define LAUNCH(MT, WKV)                                                                                   \
-    hipLaunchKernelGGL((w8a8_int8_gemm_kernel<MT, WKV>), grid, dim3(64 * WKV), 0, st, (const int8_t*)a_int8, \
-                       a_scale, (const int8_t*)b_int8, b_scale, bias, bias_dtype, out, out_dtype, (int)M,    \
-                       (int)N, (int)K, mbase)
-#define LAUNCH_WK(MT)                  \
-    switch (WK) {                      \
-        case 8: LAUNCH(MT, 8); break;  \
-        case 4: LAUNCH(MT, 4); break;  \
-        case 2: LAUNCH(MT, 2); break;  \
-        default: LAUNCH(MT, 1); break; \
-    }
-    for (int64_t mb = 0; mb < M; mb += 32) {
-        const int mbase = (int)mb;
-        if (M - mb <= 16) { LAUNCH_WK(1) } else { LAUNCH_WK(2) }
-    }
-#undef LAUNCH_WK
-#undef LAUNCH
+    const dim3 grid((unsigned)((N + 15) / 16));
+    stream_walk_m<32>(M, w8a8_int8_wk(N, K), [&](int m_base, auto mt, auto wk) {
+        constexpr int MT = decltype(mt)::value, WK = decltype(wk)::value;
+        hipLaunchKernelGGL((w8a8_int8_gemm_kernel<MT, WK>), grid, dim3(64 * WK), 0, st, (const int8_t*)a_int8, a_scale,
+                           (const int8_t*)b_int8, b_scale, bias, bias_dtype, out, out_dtype, (int)M, (int)N, (int)K, m_base);
+    });
     CHITU_RETURN_LAUNCH_STATUS();
 }

@@ -765,8 +765,9 @@ def bf16_add_norm_fits(M: int, N: int, K: int) -> bool:
 
 
 def fp8_linear_add_norm_fits(M: int, N: int, K: int, terms: int = 1) -> bool:
-    """Shapes chitu_hip_fp8_gemm_add_norm takes (mirrors its launcher and fp8_gemm.hip::plan_split): one row (two without a
-    terms sum), K a multiple of 128 up to 8192, a GEMM that runs as one workgroup per 16 output rows with >= 4 waves."""
+    """Shapes chitu_hip_fp8_gemm_add_norm takes (mirrors its launcher and csrc/gemm_plan.h::fp8_split_plan, the source of the
+    rule; tests/test_dense_exact_host.py holds the two against each other): one row (two without a terms sum), K a multiple
+    of 128 up to 8192, a GEMM that runs as one workgroup per 16 output rows with >= 4 waves."""
     if not ((M == 1 or (M == 2 and terms == 1)) and K % 128 == 0 and 128 <= K <= 8192 and 1 <= terms <= 16):
         return False
     tiles, kb = (N + 15) // 16, K // 128

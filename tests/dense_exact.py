@@ -277,7 +277,7 @@ def assert_equal(got, want, what):
 
 # ---------------------------------------------------------------- host mirrors of the launchers' plans
 def plan_split(N, K):
-    """fp8_gemm.hip::plan_split: (WK, S)."""
+    """gemm_plan.h::fp8_split_plan: (WK, S)."""
     tiles, kb = (N + 15) // 16, (K + 127) // 128
     t = max(1, min(kb, (1536 + tiles - 1) // tiles))
     wk = 1

@@ -226,7 +226,7 @@ def ident_fp8_weight(K):
 
 # ---------------------------------------------------------------- host mirrors of the launchers' choice of instantiation
 def fp8_norm_wk(N, K):
-    """fp8_norm_gemm.hip::fp8_norm_gemm_wk: 8, 4, or 0 = not served."""
+    """gemm_plan.h::fp8_norm_gemm_wk: 8, 4, or 0 = not served."""
     tiles, kb = (N + 15) // 16, K // 128
     t = max(1, min(kb, (1536 + tiles - 1) // tiles))
     wk = 1

@@ -7,10 +7,14 @@
 4. sensitivity: six mutations of the reference's inputs each change the expectation in every case, under the very comparison
    the GPU tests make (torch.equal on the fp32 output, which every GPU case takes besides its own output type);
 5. the host mirror of plan_split gives S > 1 exactly for the shapes of the in-library split, and the case lists cover every
-   value and pair they promise.
+   value and pair they promise;
+6. csrc/gemm_plan.h, compiled by a host compiler into a stand-alone driver, gives the plans of these mirrors.
 """
 
 import itertools
+import os
+import shutil
+import subprocess
 
 import pytest
 import torch
@@ -19,6 +23,7 @@ from oracle import fp8 as ofp8
 from oracle import w8a8 as ow
 from tests import cpu_ops_shim as shim
 from tests import dense_exact as dx
+from tests import fused_exact as fx
 
 FP8_SHAPES = dx.fp8_shapes()
 SOFT_SHAPES = sorted({(m, n, k, 4) for m, n, k, _ in dx.H_CASES} | {(m, n, k, lim) for m, n, k, lim, _ in dx.D_CASES})
@@ -352,3 +357,126 @@ def test_case_lists_cover_every_value_and_pair():
     assert {(c[3], c[4]) for c in dx.F_TILED} == set(itertools.product([1, 3, 4], [64, 128]))
     assert {(c[0], c[1]) for c in dx.F_TILED} == {(256, 136), (257, 264), (300, 8), (129, 1032)}
     assert {(c[3], c[4]) for c in dx.F_SPLIT} == set(itertools.product([3, 8], [-1, 2, 4, 8])) and {c[0] for c in dx.F_SPLIT} == {1, 16, 17, 33, 255}
+
+
+# ---------------------------------------------------------------- csrc/gemm_plan.h against the mirrors
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HOST_CXX = "/opt/rocm/llvm/bin/clang++" if os.path.exists("/opt/rocm/llvm/bin/clang++") else shutil.which("c++")
+FORCED = [-1, 1, 2, 4, 8]
+PLAN_DRIVER = r"""
+#include <cstdio>
+#include <initializer_list>
+#include "gemm_plan.h"
+using namespace chitu;
+int main() {
+    char mode;
+    long a, b;
+    auto show = [](int mb, auto mt, auto wk) { printf("%d:%d:%d ", mb, decltype(mt)::value, decltype(wk)::value); };
+    while (scanf(" %c %ld %ld", &mode, &a, &b) == 3) {
+        if (mode == 'w') {  // a rows under WK b: (m_base, MT, WK) of every pass, 32-row then 64-row passes
+            stream_walk_m<32>(a, (int)b, show);
+            printf("| ");
+            stream_walk_m<64>(a, (int)b, show);
+            printf("\n");
+            continue;
+        }
+        const long N = a, K = b;
+        const SplitPlan p = fp8_split_plan(N, K);
+        printf("%d %d %d", p.WK, p.S, fp8_norm_gemm_wk(N, K));
+        if (mode == 'p') {  // every other rule; a workspace that holds any split, then none
+            for (long ws : {1l << 62, 0l})
+                for (int forced : {-1, 1, 2, 4, 8}) {
+                    const SplitPlan q = fp8_stream_plan(1, N, K, ws, forced);
+                    printf(" %d %d %d %d", q.WK, q.S, (int)fp8_deep(q, K, -1), (int)fp8_deep(q, K, 0));
+                }
+            const SplitPlan q = fp8_plan_in_workspace(1, N, K, 0);
+            printf(" %d %d", q.WK, q.S);
+            for (int s : {2, 3, 16}) printf(" %d", fp8_partials_plan(K, s).WK);
+            printf(" %d", w8a8_int8_wk(N, K));
+            for (int s : {1, 3, 8}) printf(" %d", stream_wk((N + 15) / 16, K / 64, s));
+        }
+        printf("\n");
+    }
+}
+"""
+
+
+def _plan_grid():
+    nk = {(c[1], c[2]) for c in dx.A_CASES + dx.B_CASES + dx.C_CASES + dx.H_CASES} | {(n, k) for n, k, _ in dx.D_SHAPES}
+    nk |= set(dx.J_SHAPES) | {(c[2], c[3]) for c in fx.D_CASES} | {(c[2], c[3]) for c in fx.D_REFUSED if c[3] % 128 == 0}
+    nk |= {(2112, 7168), (3072, 1536), (7168, 2048), (4608, 7168), (7168, 2304)}   # the DeepSeek shapes of tools/bench_kernels.py
+    return sorted(nk)
+
+
+def _int8_wk(N, K):
+    """The rule behind dx.J_SHAPES' comment."""
+    tiles = (N + 15) // 16
+    wk = 2 if tiles >= 1024 else 4 if tiles >= 384 else 8
+    while wk > 1 and wk > K // 128:
+        wk >>= 1
+    return wk
+
+
+def _partials_wk(K, S):
+    """The waves per plane inside dx.partials_ranges."""
+    KB = K // 128
+    return 8 if KB >= 8 * S else 4 if KB >= 4 * S else 2 if KB >= 2 * S else 1
+
+
+@pytest.mark.skipif(not HOST_CXX or not os.path.exists(HOST_CXX), reason="needs a host C++ compiler")
+def test_gemm_plan_header_gives_the_plans_of_the_mirrors(tmp_path):
+    """gemm_plan.h is the one C++ statement of the launch rules; the mirrors of dense_exact / fused_exact and
+    ops.fp8_linear_add_norm_fits stay independent statements, and here they are held against each other.  The sweep shows
+    that the fused entry's refusal `fp8_split_plan gives S > 1` is the predicate it replaced, `tiles * WK < 256 and
+    N * K >= 24 Mi`, over every K the entry admits (and that over K = 128 * 2^i, 50816, 28672 with under 300 tiles the
+    predicate never holds with S == 1): fx.fp8_norm_wk still states the predicate."""
+    from chitu_amd import ops
+
+    (tmp_path / "driver.cpp").write_text(PLAN_DRIVER)
+    res = subprocess.run([HOST_CXX, "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "chitu_amd", "csrc"),
+                          str(tmp_path / "driver.cpp"), "-o", str(tmp_path / "driver")], capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    grid = _plan_grid()
+    sweep = [(16 * t, k) for k in range(128, 8192 + 1, 128) for t in range(1, 4096 + 1)]
+    wide = [(16 * t, k) for k in [128 << i for i in range(14)] + [50816, 28672] for t in range(1, 300)]
+    ms = sorted({c[0] for c in dx.A_CASES + dx.B_CASES + dx.C_CASES + dx.H_CASES + dx.J_CASES} | set(range(1, 70)) | {255, 256})
+    walks = [(m, wk) for m in ms for wk in (1, 2, 4, 8)]
+    text = "".join(f"p {n} {k}\n" for n, k in grid) + "".join(f"n {n} {k}\n" for n, k in sweep + wide)
+    text += "".join(f"w {m} {wk}\n" for m, wk in walks)
+    res = subprocess.run([str(tmp_path / "driver")], input=text, capture_output=True, text=True)
+    assert res.returncode == 0, res.stderr
+    lines = res.stdout.split("\n")
+    assert len(lines) == len(grid) + len(sweep) + len(wide) + len(walks) + 1
+
+    for (N, K), line in zip(grid, lines):
+        got = [int(v) for v in line.split()]
+        wk, s = dx.plan_split(N, K)
+        want = [wk, s, fx.fp8_norm_wk(N, K)]
+        for s_eff in (s, 1):
+            for forced in FORCED:
+                w = dx.fp8_wk(N, K, forced, s_eff)
+                want += [w, s_eff, int(w == 8 and 4 < (K // 128) // (w * s_eff) <= 8), 0]
+        want += [wk, 1] + [_partials_wk(K, sp) for sp in (2, 3, 16)] + [_int8_wk(N, K)]
+        want += [dx.bf16_wk(N, K, -1, sp) for sp in (1, 3, 8)]
+        assert got == want, (N, K, got, want)
+    for n, k, _ in dx.D_SHAPES:
+        assert dx.plan_split(n, k)[1] > 1   # the grid holds in-library splits
+    assert [_int8_wk(n, k) for n, k in dx.J_SHAPES] == [1, 4, 2, 1, 2]
+    for m, n, k, s in dx.C_CASES:
+        assert (dx.partials_ranges(k, s)[1][0] // 128) == (k // 128) * _partials_wk(k, s) // (s * _partials_wk(k, s))
+
+    refused_by_split = 0
+    for (N, K), line in zip(sweep + wide, lines[len(grid):]):
+        wk, s, norm_wk = (int(v) for v in line.split())
+        assert (wk, s) == dx.plan_split(N, K) and norm_wk == fx.fp8_norm_wk(N, K), (N, K, line)
+        predicate = ((N + 15) // 16) * wk < 256 and N * K >= (24 << 20)
+        assert not (predicate and s == 1), (N, K)
+        refused_by_split += predicate
+        if K <= 8192:
+            assert not predicate and ops.fp8_linear_add_norm_fits(1, N, K) == (norm_wk != 0), (N, K)
+    assert refused_by_split > 0   # (outside the fused entry's K range the predicate does hold, always with S > 1)
+
+    for (M, WK), line in zip(walks, lines[len(grid) + len(sweep) + len(wide):]):
+        got32, got64 = ([tuple(int(v) for v in p.split(":")) for p in half.split()] for half in line.split("|"))
+        assert got32 == [(M - r, dx.bf16_tile_form(r), WK) for r in dx.passes(M, 32)], (M, WK, got32)
+        assert got64 == [(M - r, dx.fp8_tile_form(r), WK) for r in dx.passes(M, 64)], (M, WK, got64)

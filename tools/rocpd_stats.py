@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Summarise a rocprofv3 rocpd (.db) kernel trace: per-kernel calls / total / avg / min / max (us).
-Usage: python tools/rocpd_stats.py <results.db> [--last-fraction F] > profiles/<name>.txt"""
+Usage: python tools/rocpd_stats.py <results.db> [--last-fraction F] > profiles/<name>.txt
+       python tools/rocpd_stats.py <results.db> --launches   # the multiset of (kernel, grid, workgroup) and its sha256:
+                                                             # equal between two builds = the same launches"""
+import hashlib
 import sqlite3
 import sys
 
@@ -10,6 +13,14 @@ con = sqlite3.connect(db)
 cur = con.cursor()
 cols = [r[1] for r in cur.execute("pragma table_info(kernels)")]
 name_col = "name" if "name" in cols else "kernel_name"
+if "--launches" in sys.argv:
+    rows = cur.execute(f"select {name_col}, grid_x, grid_y, grid_z, workgroup_x, workgroup_y, workgroup_z, count(*) from kernels "
+                       "group by 1, 2, 3, 4, 5, 6, 7 order by 1, 2, 3, 4, 5, 6, 7").fetchall()
+    lines = [f"{c:8d}  grid {gx} x {gy} x {gz}  workgroup {wx} x {wy} x {wz}  {n}" for n, gx, gy, gz, wx, wy, wz, c in rows]
+    print(f"# {db}: {sum(r[-1] for r in rows)} dispatches, {len(rows)} distinct launches, sha256 "
+          f"{hashlib.sha256(chr(10).join(lines).encode()).hexdigest()}")
+    print("\n".join(lines))
+    sys.exit(0)
 rows = cur.execute(f"select {name_col}, start, end from kernels order by start").fetchall()
 if frac < 1.0:
     rows = rows[int(len(rows) * (1 - frac)):]
