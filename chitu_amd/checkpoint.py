@@ -395,6 +395,34 @@ def map_mixtral_names(state: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tens
     return out
 
 
+# glm-4-9b-chat's files carry the key names of its remote ("custom code") ChatGLM modules (model_hf_llama.py:577-596 lists the
+# same checkpoint facts).  qkv and gate | up are shipped merged under these names; split_merged_* below take them from there.
+_GLM4_NAMES = (("transformer.embedding.word_embeddings.", "embed_tokens."), ("transformer.encoder.final_layernorm.", "norm."),
+               ("transformer.output_layer.", "lm_head."), ("transformer.encoder.layers.", "layers."),
+               (".self_attention.query_key_value.", ".self_attn.qkv_proj."), (".self_attention.dense.", ".self_attn.o_proj."),
+               (".mlp.dense_h_to_4h.", ".mlp.gate_up_proj."), (".mlp.dense_4h_to_h.", ".mlp.down_proj."))
+_GLM4_DROPPED = ("transformer.rotary_pos_emb.inv_freq",)  # recomputed: precompute_freqs_cis(rotary_dim, ...)
+
+
+def map_glm4_names(state: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """ChatGLM remote-code key names -> the HF Llama-family names preprocess_hf_llama expects (without the `model.` prefix, which
+    it strips anyway).  The rotary module's inv_freq buffer is dropped; a `transformer.` name left unmapped is an error, not a
+    tensor carried along to fail later."""
+    out = {}
+    for k, v in state.items():
+        if k in _GLM4_DROPPED:
+            continue
+        new = k
+        for a, b in _GLM4_NAMES:
+            new = new.replace(a, b)
+        if new.startswith("transformer."):
+            raise KeyError(f"unknown GLM-4 checkpoint name '{k}'")
+        if new in out:
+            raise KeyError(f"'{k}' maps onto '{new}', which is present already")
+        out[new] = v
+    return out
+
+
 def _split_merged(state: Mapping[str, torch.Tensor], merged: str, parts, sizes_of) -> Dict[str, torch.Tensor]:
     """`<p>.merged.{weight,bias}` -> `<p>.part.{weight,bias}` for part in parts, split along dim 0 into sizes_of(tensor)."""
     out = {}
@@ -540,6 +568,8 @@ def load_checkpoint_hf_llama(model, path: str, rank: int = 0, world: int = 1, sk
         load_deepseek_v3(model, state)
         return
     mixtral = hasattr(args, "num_local_experts")
+    if any(k.startswith("transformer.") for k in state):  # glm-4-9b-chat under its ChatGLM names
+        state = map_glm4_names(state)
     if getattr(args, "tie_word_embeddings", False) and "lm_head.weight" not in state:
         # the small Qwen3 sizes ship no output head: it is the embedding (sharded by vocabulary rows like it below)
         state["lm_head.weight"] = state["model.embed_tokens.weight" if "model.embed_tokens.weight" in state else "embed_tokens.weight"]

@@ -112,7 +112,7 @@ def _fuses_norm(x, pending, n_out, two_terms_ok: bool = False, weight=None) -> b
 class LlamaAttention(torch.nn.Module):
     def __init__(self, args, layer_id, cache, attn_backend, device=None, rotary_type="llama"):
         super().__init__()
-        self.rotary_type = rotary_type  # "llama" (Meta original, interleaved) | "hf-llama" (half split)
+        self.rotary_type = rotary_type  # "llama" (Meta original, interleaved) | "hf-llama" (half split) | "glm4" (partial interleaved)
         t = tp.get_tp_size()
         self.layer_id, self.cache, self.attn_backend = layer_id, cache, attn_backend
         self.hd = args.head_dim
@@ -145,6 +145,14 @@ class LlamaAttention(torch.nn.Module):
             if self.hd != 128:
                 raise ValueError(f"qkv_bias: the bias launches are head_dim 128, got {self.hd} (Qwen2.5-0.5B has 64)")
             self.bqkv = _param((self.hq + 2 * self.hkv) * self.hd, device=device)
+        # GLM-4: interleaved pairs over the first rotary_dim channels of a head (the width of the decoder's cos / sin table), the
+        # rest pass through.  Only the bias launches take a rotary width (include/chitu_hip_ext7.h).
+        if rotary_type == "glm4":
+            if self.qk_norm:
+                raise ValueError("rotary_type 'glm4' with qk_norm: the head-norm launches rotate all 128 channels (no partial width)")
+            if not self.qkv_bias:
+                raise ValueError("rotary_type 'glm4' needs qkv_bias: the partial rotary width exists in the bias launches only "
+                                 "(GLM-4-9B has a q / k / v bias)")
 
     def decode_forward_paged(self, x, cos, sin, q_len=1):
         """x = attn_norm(h) bf16 [bs, dim] -> wo(attention) before the all-reduce (model.py:167-198)."""
@@ -334,7 +342,8 @@ class LlamaDecoder(torch.nn.Module):
         self.layers = torch.nn.ModuleList(block(i, args, cache, attn_backend, device) for i in range(args.n_layers))
         self.norm = _param(args.dim, device=device)
         self.head_weight = _param(self.vocab_local, args.dim, device=device)
-        cos, sin = precompute_freqs_cis(args.head_dim, max_position_embeddings, args.rope_theta)
+        # rotary_dim: the channels of a head that rotate (GLM-4: 64 of 128); every other model has no such field
+        cos, sin = precompute_freqs_cis(getattr(args, "rotary_dim", args.head_dim), max_position_embeddings, args.rope_theta)
         self.cos_table, self.sin_table = cos.to(device), sin.to(device)
         self.graphs, self.static_tokens, self.static_out = {}, {}, {}
         self.graph_pool = None

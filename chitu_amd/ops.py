@@ -398,8 +398,11 @@ def apply_rotary_pos_emb(q, k, cos, sin, rotary_type="hf-llama"):
 
     rotary_type "llama": interleaved (re, im) pairs (DeepSeek MLA); "hf-llama": half-split.
     cos/sin are fp32 [bs, d/2].  Math in fp32, one rounding to the input dtype.
+    "glm4" (GLM-4-9B): interleaved pairs over the first R = 2 * cos.shape[-1] channels of every head, the rest copied --
+    Hugging Face's modeling_glm.apply_rotary_pos_emb, NOT the reference's torch branch (docs/design/4_parity.md); bf16, d 128,
+    cos / sin [bs, R / 2] (chitu_ext7_rope).
     """
-    if rotary_type not in ("llama", "hf-llama"):
+    if rotary_type not in ("llama", "hf-llama", "glm4"):
         raise ValueError(f"Unknown rotary type: {rotary_type}")
     require_cuda(q, k, cos, sin)
     assert cos.dtype == torch.float32 and sin.dtype == torch.float32
@@ -407,7 +410,9 @@ def apply_rotary_pos_emb(q, k, cos, sin, rotary_type="hf-llama"):
     assert q.stride(-1) == 1 and k.stride(-1) == 1
     bs = q.shape[0]
     d = q.shape[-1]
-    assert cos.shape == (bs, d // 2), f"{cos.shape} {q.shape}"
+    partial = rotary_type == "glm4"
+    half = cos.shape[-1] if partial else d // 2
+    assert cos.shape == (bs, half) and sin.shape == (bs, half), f"{cos.shape} {q.shape}"
     assert q.dim() == 3 and k.dim() in (2, 3)
     out_q = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     out_k = torch.empty(k.shape, dtype=k.dtype, device=k.device)
@@ -417,12 +422,12 @@ def apply_rotary_pos_emb(q, k, cos, sin, rotary_type="hf-llama"):
     ok_sb = out_k.stride(0)
     ok_sh = 0 if k.dim() == 2 else out_k.stride(1)
     check(
-        _lib.lib().chitu_hip_rope(
+        getattr(_lib.lib(), "chitu_ext7_rope" if partial else "chitu_hip_rope")(
             ptr(q), ptr(k), ptr(out_q), ptr(out_k), ptr(cos), ptr(sin), float_dtype_code(q.dtype),
             i32(bs), i32(q.shape[1]), i32(kh), i32(d),
             i64(q.stride(0)), i64(q.stride(1)), i64(k_sb), i64(k_sh),
             i64(out_q.stride(0)), i64(out_q.stride(1)), i64(ok_sb), i64(ok_sh),
-            i32(0 if rotary_type == "llama" else 1), stream_ptr(),
+            i32(1 if rotary_type == "hf-llama" else 0), *((i32(2 * half),) if partial else ()), stream_ptr(),
         ),
         "apply_rotary_pos_emb",
     )
@@ -555,6 +560,8 @@ def bf16_linear(x: torch.Tensor, weight: torch.Tensor, out_dtype=None) -> torch.
 def gqa_qkv_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, rotary_type="llama"):
     """RoPE(q in place, k) + append of the rotated k and of v to their pages in one launch (GQA / MHA
     decode).  qkv [bs, q_heads + 2*kv_heads, head_dim] bf16 (merged projection output); returns the q view."""
+    if rotary_type not in ("llama", "hf-llama"):  # "glm4" rotates a part of the head: only the bias entries take a width
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
     require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens)
     assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[1] == q_heads + 2 * kv_heads
     assert k_cache.is_contiguous() and v_cache.is_contiguous() and k_cache.shape == v_cache.shape and k_cache.dtype == torch.bfloat16
@@ -577,6 +584,8 @@ def gqa_qkv_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page
     """gqa_qkv_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): RoPE(q in place, k), the rotated k rounded
     to bf16 as gqa_qkv_post rounds it and quantised, v quantised, both written straight into their page rows -- the bytes of
     gqa_kv_quant_fp8 on the rows gqa_qkv_post writes.  One launch; returns the q view."""
+    if rotary_type not in ("llama", "hf-llama"):
+        raise ValueError(f"Unknown rotary type: {rotary_type}")
     require_cuda(qkv, cos, sin, k_cache, v_cache, page_table, old_seq_lens)
     assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.is_contiguous() and qkv.shape[1] == q_heads + 2 * kv_heads
     _check_gqa_fp8_caches(k_cache, v_cache)
@@ -609,9 +618,12 @@ def _gqa_qkv_row16_post(prefix, what, qkv, q_heads, kv_heads, cos, sin, k_cache,
     """The one body of gqa_qkv_norm_post, gqa_qkv_bias_post and their _kv_fp8 forms (csrc/qkv_post_row16.hip): entry
     prefix + what; `operands` are the tensors the entry takes besides gqa_qkv_post's, validated by check_operands(*operands);
     tail() gives its trailing ctypes arguments, in front of the stream, once the operands are validated.  A name ending in
-    _kv_fp8 takes the fp8 caches."""
-    if rotary_type not in ("llama", "hf-llama"):
+    _kv_fp8 takes the fp8 caches.  Prefix chitu_ext7_ (include/chitu_hip_ext7.h) is the form with a rotary width, the only one
+    that takes rotary_type "glm4": cos / sin are [bs, R / 2] and R = 2 * cos.shape[-1] goes in behind the layout."""
+    partial = prefix == "chitu_ext7_"
+    if rotary_type not in (("glm4",) if partial else ("llama", "hf-llama")):
         raise ValueError(f"Unknown rotary type: {rotary_type}")
+    half = cos.shape[-1] if partial else 64
     if what.endswith("_kv_fp8"):
         _check_gqa_fp8_caches(k_cache, v_cache)
     else:
@@ -624,12 +636,13 @@ def _gqa_qkv_row16_post(prefix, what, qkv, q_heads, kv_heads, cos, sin, k_cache,
     assert k_cache.shape[2] == kv_heads and page_table.dtype == torch.int32 and page_table.stride(1) == 1
     assert cos.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous() and old_seq_lens.dtype == torch.int32
     bs = qkv.shape[0]
-    assert cos.shape == (bs, 64) and sin.shape == (bs, 64) and page_table.shape[0] >= bs and page_table.is_contiguous()
+    assert cos.shape == (bs, half) and sin.shape == (bs, half) and page_table.shape[0] >= bs and page_table.is_contiguous()
     assert old_seq_lens.shape[0] >= bs and old_seq_lens.is_contiguous()
     check(
         getattr(_lib.lib(), prefix + what)(
             ptr(qkv), i64(qkv.stride(0)), i32(q_heads), i32(kv_heads), i32(128), ptr(cos), ptr(sin),
-            i32(0 if rotary_type == "llama" else 1), ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
+            i32(1 if rotary_type == "hf-llama" else 0), *((i32(2 * half),) if partial else ()),
+            ptr(k_cache), ptr(v_cache), i64(k_cache.shape[0]), i32(k_cache.shape[1]),
             ptr(page_table), i32(page_table.shape[1]), ptr(old_seq_lens), i32(bs), *tail(), stream_ptr(),
         ),
         what,
@@ -686,12 +699,18 @@ def qk_norm_rope(q, k, q_norm_weight, k_norm_weight, eps, cos, sin, rotary_type=
     return out_q, out_k
 
 
+def _bias_prefix(rotary_type):
+    """The bias entries of a rotary type: "glm4" alone takes the ones with a rotary width (include/chitu_hip_ext7.h)."""
+    return "chitu_ext7_" if rotary_type == "glm4" else "chitu_ext5_"
+
+
 def gqa_qkv_bias_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type="llama"):
     """gqa_qkv_post with Qwen2's q / k / v projection bias in front of the rotation, one launch: bias [(q_heads + 2 kv_heads) *
     128] bf16 is added to every row (fp32 add, one bf16 rounding: a bf16 torch.add), q and k heads are then rotated; q in place,
     k and the biased v into the token's page row.  Bit for bit gqa_qkv_post on qkv + bias.  qkv [bs, q_heads + 2*kv_heads, 128]
-    bf16 (the row stride may be padded); returns the q view."""
-    return _gqa_qkv_row16_post("chitu_ext5_", "gqa_qkv_bias_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table,
+    bf16 (the row stride may be padded); returns the q view.  rotary_type "glm4": interleaved pairs over the first
+    R = 2 * cos.shape[-1] channels of every q and k head, the rest pass through biased (chitu_ext7_gqa_qkv_bias_post)."""
+    return _gqa_qkv_row16_post(_bias_prefix(rotary_type), "gqa_qkv_bias_post", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table,
                                old_seq_lens, rotary_type, (bias,), lambda b: _check_qkv_bias(b, q_heads + 2 * kv_heads),
                                lambda: (ptr(bias),))
 
@@ -699,7 +718,7 @@ def gqa_qkv_bias_post(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_t
 def gqa_qkv_bias_post_kv_fp8(qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache, page_table, old_seq_lens, bias, rotary_type="llama"):
     """gqa_qkv_bias_post over the fp8 K / V caches (uint8 [pages, page, kv_heads, 144]): the bytes of gqa_kv_quant_fp8 on the
     rows gqa_qkv_bias_post writes.  One launch; returns the q view."""
-    return _gqa_qkv_row16_post("chitu_ext5_", "gqa_qkv_bias_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
+    return _gqa_qkv_row16_post(_bias_prefix(rotary_type), "gqa_qkv_bias_post_kv_fp8", qkv, q_heads, kv_heads, cos, sin, k_cache, v_cache,
                                page_table, old_seq_lens, rotary_type, (bias,), lambda b: _check_qkv_bias(b, q_heads + 2 * kv_heads),
                                lambda: (ptr(bias),))
 
@@ -708,25 +727,29 @@ def qkv_bias_rope(qkv, q_heads, kv_heads, bias, cos, sin, rotary_type="hf-llama"
     """The prefill form of gqa_qkv_bias_post, no cache: qkv [T, q_heads + 2 kv_heads, 128] bf16 (channels dense, row and head
     strides multiples of 8 elements) plus bias, RoPE on the q and k heads, the whole prompt in one launch.  cos / sin fp32
     [T, 64].  Returns contiguous (out_q [T, q_heads, 128], out_k, out_v [T, kv_heads, 128]), bit-identical to what the decode
-    form produces for the same rows."""
-    if rotary_type not in ("llama", "hf-llama"):
+    form produces for the same rows.  rotary_type "glm4": cos / sin [T, R / 2], interleaved pairs over the first R channels
+    (chitu_ext7_qkv_bias_rope)."""
+    if rotary_type not in ("llama", "hf-llama", "glm4"):
         raise ValueError(f"Unknown rotary type: {rotary_type}")
+    partial = rotary_type == "glm4"
+    half = cos.shape[-1] if partial else 64
     require_cuda(qkv, bias, cos, sin)
     assert qkv.dtype == torch.bfloat16 and qkv.dim() == 3 and qkv.shape[1] == q_heads + 2 * kv_heads and qkv.shape[2] == 128
     assert qkv.stride(2) == 1 and qkv.stride(1) % 8 == 0 and qkv.stride(0) % 8 == 0
     _check_qkv_bias(bias, q_heads + 2 * kv_heads)
     T = qkv.shape[0]
     assert cos.dtype == torch.float32 and sin.dtype == torch.float32 and cos.is_contiguous() and sin.is_contiguous()
-    assert cos.shape == (T, 64) and sin.shape == (T, 64)
+    assert cos.shape == (T, half) and sin.shape == (T, half)
     out_q = torch.empty(T, q_heads, 128, dtype=qkv.dtype, device=qkv.device)
     out_k = torch.empty(T, kv_heads, 128, dtype=qkv.dtype, device=qkv.device)
     out_v = torch.empty(T, kv_heads, 128, dtype=qkv.dtype, device=qkv.device)
     if T == 0:
         return out_q, out_k, out_v
     check(
-        _lib.lib().chitu_ext5_qkv_bias_rope(
+        getattr(_lib.lib(), _bias_prefix(rotary_type) + "qkv_bias_rope")(
             ptr(qkv), i64(qkv.stride(0)), i64(qkv.stride(1)), ptr(bias), ptr(cos), ptr(sin), ptr(out_q), ptr(out_k), ptr(out_v),
-            i64(T), i32(q_heads), i32(kv_heads), i32(128), i32(0 if rotary_type == "llama" else 1), stream_ptr(),
+            i64(T), i32(q_heads), i32(kv_heads), i32(128), i32(1 if rotary_type == "hf-llama" else 0),
+            *((i32(2 * half),) if partial else ()), stream_ptr(),
         ),
         "qkv_bias_rope",
     )
