@@ -22,10 +22,11 @@ import os
 import torch
 import torch.nn.functional as F
 
-from . import fused_moe, graphs, ops
+from . import fused_moe, ops
 from . import tensor_parallel as tp
 from .attn_backend import MLA_MULTI_MAX_Q, HipAttnBackend
 from .cache_manager import MAX_DECODE_Q, PagedKVCacheManager, mla_kv_layout
+from .decoder import DecoderBase, VarLens  # noqa: F401  (VarLens: importable from here as before)
 
 FP8 = torch.float8_e4m3fn
 BLOCK = 128
@@ -88,21 +89,6 @@ class DeepSeekV3Args:
 
     def has_gate_bias(self):
         return self.dim == 7168 if self.gate_bias is None else self.gate_bias
-
-
-class VarLens:
-    """Ragged-batch bookkeeping of a prefill call (chitu/utils.py:84-101): same fields."""
-
-    def __init__(self, tokens, device) -> None:
-        self.cpu_lens = [len(t) for t in tokens]
-        self.cpu_prefix_lens = [0]
-        for n in self.cpu_lens:
-            self.cpu_prefix_lens.append(self.cpu_prefix_lens[-1] + n)
-        self.lens = torch.tensor(self.cpu_lens, device=device, dtype=torch.int32)
-        self.prefix_lens = torch.tensor(self.cpu_prefix_lens, device=device, dtype=torch.int32)
-        self.max_len = max(self.cpu_lens)
-        self.total_len = self.cpu_prefix_lens[-1]
-        self.position_ids = torch.cat([torch.arange(n) for n in self.cpu_lens]).to(device)
 
 
 def compute_softmax_scale(args: DeepSeekV3Args) -> float:
@@ -440,7 +426,7 @@ class AttentionDeepSeekV3(torch.nn.Module):
         rows scattered into their pages (quantised first with an fp8 cache), then the attention over the pages
         (HipAttnBackend.mla_attn_varlen_with_kvcache: gather + flash kernel) -- every query sees the cached prefix and the new
         rows up to itself.  varlens.gathered / varlens.total_keys: the gather buffer all layers share and the host-known key
-        count (DeepSeekV3Decoder.prefill_continue).
+        count (DeepSeekV3Decoder.prepare_continue_attn).
         kv_cache_dtype "fp8": everything is read back from the pages, so a chunk attends over the QUANTISED rows of its prefix
         and of itself, where one-shot prefill attends over the unquantised rows of the prompt."""
         q_abs, q_pe, _, kv_pe = self._prefill_projections(x_quant, cos, sin)
@@ -673,15 +659,15 @@ def add_norm(x, pending, norm, out_bf16=True, quant=None, tile_major=False):
     return tp.add_norm(x, pending, norm.weight, norm.eps, out_bf16=out_bf16, quant=quant, tile_major=tile_major)
 
 
-class DeepSeekV3Decoder(torch.nn.Module):
-    """Decode-only transformer: embed -> blocks -> norm -> head -> fp32 logits, with the whole
-    step captured as a hipGraph per batch size (chitu/models/model.py:538-622; no third-party
-    attention gate as at :543-546 -- the HIP backend is capture-safe by construction)."""
+class DeepSeekV3Decoder(DecoderBase):
+    """DecoderBase over MLA + MoE blocks with block-fp8 linears and a paged latent cache (chitu/models/model.py:538-622; no
+    third-party attention gate as at :543-546 -- the HIP backend is capture-safe by construction)."""
+
+    multi_max_q = MLA_MULTI_MAX_Q  # chitu_hip_mla_decode_multi reads each sequence's pages ceil(T / 2) times
 
     def __init__(self, args: DeepSeekV3Args, cache: PagedKVCacheManager, attn_backend: HipAttnBackend,
                  max_position_embeddings: int = 4096, device="cuda", layers: Optional[List[int]] = None):
-        super().__init__()
-        self.args, self.cache, self.attn_backend, self.device = args, cache, attn_backend, torch.device(device)
+        super().__init__(args, cache, attn_backend, device)
         deg = args.tp_degree()
         assert args.vocab_size % deg == 0
         self.vocab_local = args.vocab_size // deg
@@ -706,149 +692,9 @@ class DeepSeekV3Decoder(torch.nn.Module):
         self.head_weight = torch.nn.Parameter(torch.empty(self.vocab_local, args.dim, dtype=torch.bfloat16, device=device), requires_grad=False)
         cos, sin = precompute_freqs_cis(args, max_position_embeddings)
         self.cos_table, self.sin_table = cos.to(device), sin.to(device)
-        self.graphs, self.static_tokens, self.static_out = {}, {}, {}
-        self.graph_pool = None
 
-    def decode_eager(self, tokens, q_len=1):
-        """tokens [bs] int64 -> logits [bs, vocab] fp32 (decode_single_device, model.py:468-475).  q_len > 1: the rows are q_len
-        consecutive tokens of each sequence, positions and page rows from the cache manager's multi-token buffers."""
-        # embedding rows of this rank's vocabulary slice + every row's rotary row (prepare_freqs_cis_decode,
-        # model.py:429-448): one launch
-        positions = self.cache.get_gpu_multi_row_lens() if q_len > 1 else self.cache.get_gpu_seq_lens_excl_this_decode()
-        h, cos, sin = ops.embed_rope_gather(tokens, self.embed_weight, self.vocab_start if self.vocab_local != self.args.vocab_size else 0,
-                                            positions, self.cos_table, self.sin_table)
-        if self.vocab_local != self.args.vocab_size:
-            h = tp.all_reduce(h)  # tensor_parallel.py:199-208
-        pending = None
-        for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin, q_len=q_len)
-        h = add_norm(h, pending, self.norm)[1]
-        # bf16 logits -> fp32 (model.py:475), the cast riding in the gather
-        return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
-
-    @torch.inference_mode()
-    def prefill(self, tokens, req_ids, chunk_size=None):
-        """tokens: list of per-request token-id lists; req_ids: their cache keys.  Runs the prompt
-        through every layer, fills the KV pages, returns fp32 logits [n_req, vocab] of each prompt's
-        LAST token (prefill_single_device, model.py:451-465).  Eager launches.
-        chunk_size = c: the first c tokens of every prompt run here, the rest in rounds of prefill_continue with at most c tokens
-        per request (a request whose prompt is exhausted leaves the later rounds), so no round holds more than n_req * c rows
-        (LlamaDecoder.prefill's rule).  With kv_cache_dtype "fp8" the later chunks attend over quantised rows (prefill_continue)."""
-        if chunk_size is not None:
-            c = int(chunk_size)
-            if c < 1:
-                raise ValueError(f"chunk_size={chunk_size}: at least one token per round")
-            req_ids = list(req_ids)
-            logits = self.prefill([list(t[:c]) for t in tokens], req_ids)
-            done = c
-            while True:
-                live = [i for i, t in enumerate(tokens) if len(t) > done]
-                if not live:
-                    return logits
-                out = self.prefill_continue([list(tokens[i][done : done + c]) for i in live], [req_ids[i] for i in live])
-                logits[torch.tensor(live, device=logits.device)] = out  # a later round overwrites it until the prompt ends
-                done += c
-
-        from . import graphs
-
-        graphs.sweep_if_memory_was_recycled()  # the eager path's canary: once after an xGMI communicator came or went
-        varlens = VarLens(tokens, self.device)
-        self.cache.curr_varlens, self.cache.curr_req_ids = varlens, list(req_ids)
-        flat = torch.tensor([t for seq in tokens for t in seq], dtype=torch.int64, device=self.device)
-        cos, sin = self.cos_table[varlens.position_ids], self.sin_table[varlens.position_ids]
-        h, pending = self.embed(flat), None
-        for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin, varlens)
-        self.cache.finalize_cache_all_prefill(req_ids, varlens)
-        return self._last_token_logits(h, pending, varlens)
-
-    def _last_token_logits(self, h, pending, varlens):
-        """The final norm and the head on the last row of every sequence of a prefill call."""
-        last = torch.tensor([p - 1 for p in varlens.cpu_prefix_lens[1:]], dtype=torch.int64, device=self.device)
-        h = h[last]
-        pending = tp.resolve(pending)
-        if pending is not None:
-            pending = pending[last].contiguous()
-        h = add_norm(h, pending, self.norm)[1]
-        return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
-
-    @torch.inference_mode()
-    def prefill_continue(self, tokens, req_ids):
-        """Ragged chunks of new tokens for requests that are already cached (a conversation's next turn, the next chunk of a
-        long prompt, a draft model's catch-up) -> fp32 logits [n_req, vocab] of each chunk's last token; appends their latent
-        rows.  Positions, and so cos / sin, continue from each request's cached length.  The attention reads the pages
-        (AttentionDeepSeekV3.prefill_forward_paged: one gather + one flash launch per layer, the gather buffer allocated here
-        once and shared by the layers); everything else is prefill's stack on the new rows, tensor- and expert-parallel paths
-        included.  An unknown request, a chunk that overruns the rotary table or the block table, or too few free pages raises
-        before any cache state changes.
-        kv_cache_dtype "fp8": the chunk attends over the quantised rows of its prefix AND of itself (everything is read back
-        from the pages), where one-shot prefill attends over the unquantised prompt -- the numbers of a chunked fp8 prefill are
-        those of prefill + token-by-token decode, not those of the one-shot call."""
-        from . import graphs
-
-        req_ids = list(req_ids)
-        assert len(tokens) == len(req_ids) and all(len(t) >= 1 for t in tokens)
-        for r, t in zip(req_ids, tokens):
-            if r not in self.cache.seq_lens:
-                raise KeyError(f"request {r!r} is not cached: a continued prefill extends a sequence that prefill registered")
-            assert self.cache.seq_lens[r] + len(t) <= self.cos_table.shape[0], \
-                f"request {r!r}: {self.cache.seq_lens[r]} + {len(t)} tokens exceed max_position_embeddings={self.cos_table.shape[0]}"
-        graphs.sweep_if_memory_was_recycled()
-        varlens = VarLens(tokens, self.device)
-        varlens.continued = True
-        self.cache.prepare_cache_prefill_continue(req_ids, varlens)
-        varlens.total_keys = sum(self.cache.seq_lens[r] + len(t) for r, t in zip(req_ids, tokens))
-        varlens.gathered = torch.empty(varlens.total_keys, self.args.kv_lora_rank + self.args.qk_rope_head_dim, dtype=torch.bfloat16,
-                                       device=self.device)
-        pos = self.cache.get_continue_position_ids()
-        flat = torch.tensor([t for seq in tokens for t in seq], dtype=torch.int64, device=self.device)
-        cos, sin = self.cos_table[pos], self.sin_table[pos]
-        h, pending = self.embed(flat), None
-        for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin, varlens)
-        self.cache.finalize_cache_all_prefill_continue(req_ids)
-        return self._last_token_logits(h, pending, varlens)
-
-    @torch.inference_mode()
-    def generate(self, prompts, max_new_tokens, req_ids=None, use_graph=True, temperatures=None, top_ks=None,
-                 top_ps=None, frequency_penalties=None, generator=None, prefill_chunk_size=None):
-        """Prefill (prefill_chunk_size: in chunks, prefill's chunk_size), then max_new_tokens - 1 decode steps; returns
-        [n_req, max_new_tokens] int64 and frees the
-        requests' pages.  Token selection is executor.py:82-112 on the device (chitu_amd.sampling): greedy
-        unless some top_k > 1 (then per-request temperature / top-k / top-p sampling, uniforms from
-        `generator`), with an optional per-request frequency penalty; tokens never visit the host."""
-        from .sampling import DeviceSampler
-
-        req_ids = [f"gen{i}" for i in range(len(prompts))] if req_ids is None else list(req_ids)
-        pick = DeviceSampler(len(prompts), max_new_tokens, self.device, temperatures, top_ks, top_ps,
-                             frequency_penalties, generator)
-        tok = pick(self.prefill(prompts, req_ids) if prefill_chunk_size is None else
-                   self.prefill(prompts, req_ids, chunk_size=prefill_chunk_size))
-        out = [tok]
-        for _ in range(max_new_tokens - 1):
-            self.cache.prepare_cache_decode(req_ids)
-            self.cache.prepare_block_table_for_decode(req_ids)
-            tok = pick(self.decode(tok, use_graph=use_graph))
-            self.cache.finalize_cache_single_decode(req_ids)
-            out.append(tok)
-        for r in req_ids:
-            self.cache.finalize_cache_all_decode(r)
-        tokens_out = torch.stack(out, dim=1)
-        if tp.xgmi_comm() is not None:
-            # the tokens are about to leave the engine: make sure no collective behind them gave up on a peer
-            torch.cuda.current_stream().synchronize()
-            tp.check_comm()
-        return tokens_out
-
-    def embed(self, tokens):
-        """tensor_parallel.py:199-208: mask ids outside this rank's vocab slice, lookup, all-reduce."""
-        if self.vocab_local == self.args.vocab_size:
-            return F.embedding(tokens, self.embed_weight)
-        local = tokens - self.vocab_start
-        mask = (local < 0) | (local >= self.vocab_local)
-        y = F.embedding(torch.where(mask, torch.zeros_like(local), local), self.embed_weight)
-        y = torch.where(mask.unsqueeze(-1), torch.zeros_like(y), y)
-        return tp.all_reduce(y)
+    def final_norm(self):
+        return self.norm.weight, self.norm.eps
 
     def prepare_decoding_attn(self):
         """model_deepseek_v3.py:1339-1350 -- outside the graph."""
@@ -857,101 +703,18 @@ class DeepSeekV3Decoder(torch.nn.Module):
             c.get_gpu_seq_lens_excl_this_decode(), c.get_gpu_seq_lens_incl_this_decode(),
             c.get_gpu_block_table(), c.get_block_size(), softmax_scale=compute_softmax_scale(self.args))
 
-    @torch.inference_mode()
-    def decode(self, tokens, use_graph=True):
-        """One decode step -> fp32 logits [bs, vocab].  use_graph: False = eager launches; True = replay of
-        the step captured per batch size -- as ONE hipGraph when this rank has no collectives (or when
-        CHITU_TP_GRAPH=full asks for the collectives to be captured too), else PIECEWISE: the step is cut at
-        every all-reduce / all-gather, the pieces are hipGraphs and the collectives are issued between them
-        (RCCL never has to be capturable; 2 x layers + 2 host calls per step, far below the pieces' GPU
-        time); "piecewise" / "full" force a mode."""
-        tp.check_comm()  # a collective of an earlier step that timed out: raise instead of decoding garbage
-        self.prepare_decoding_attn()
-        bs = tokens.shape[0]
-        if not use_graph or tp.xgmi_split_phase():  # (split-phase collectives hold a host barrier: not capturable)
-            return self.decode_eager(tokens)
-        mode = graphs.graph_mode(use_graph)
-        key = (bs, mode)
-        if bs not in self.static_tokens:
-            self.static_tokens[bs] = tokens.clone()
-        else:
-            self.static_tokens[bs].copy_(tokens)
-        if key not in self.graphs:
-            # Eager step on the static inputs (it replicates the graph's side effect, the append at position L, which the
-            # replays then overwrite with the same values), capture, ONE replay checked bit for bit against that eager
-            # step (graphs.capture_verified): a graph that does not reproduce the eager launches is never used.
-            g, self.graph_pool, self.static_out[bs] = graphs.capture_verified(
-                lambda: self.decode_eager(self.static_tokens[bs]), self.static_out.get(bs), mode, self.graph_pool,
-                what=f"DeepSeekV3Decoder decode step bs={bs}")
-            self.graphs[key] = g
-        self.graphs[key].replay()
-        return self.static_out[bs]
+    def prepare_continue_attn(self, varlens, req_ids):
+        """AttentionDeepSeekV3.prefill_forward_paged runs one gather + one flash launch per layer: the host-known key count
+        and the gather buffer, allocated here once and shared by the layers.  (kv_cache_dtype "fp8": the chunk attends over the
+        quantised rows of its prefix AND of itself, where one-shot prefill attends over the unquantised prompt -- the numbers of
+        a chunked fp8 prefill are those of prefill + token-by-token decode, not those of the one-shot call.)"""
+        varlens.total_keys = sum(self.cache.seq_lens[r] + n for r, n in zip(req_ids, varlens.cpu_lens))
+        varlens.gathered = torch.empty(varlens.total_keys, self.args.kv_lora_rank + self.args.qk_rope_head_dim, dtype=torch.bfloat16,
+                                       device=self.device)
 
-    @torch.inference_mode()
-    def decode_multi(self, tokens, use_graph=True):
-        """One step over T = tokens.shape[1] tokens per sequence (1 < T <= 8): tokens [bs, T] int64 are appended at each
-        sequence's length .. + T - 1 and token t attends to everything up to itself -- the verify step of speculative decoding
-        (LlamaDecoder.decode_multi's contract).  Returns fp32 logits [bs, T, vocab]: row (b, t) predicts the token after
-        tokens[b, t].  The caller has run cache.prepare_block_table_for_decode_multi(req_ids, T) and settles the lengths with
-        finalize_cache_multi_decode.
-
-        The stack runs on bs * T rows with per-row positions (the fused small-batch launches apply by their row limits on
-        bs * T); only the attention knows T: chitu_hip_mla_decode_multi reads each sequence's pages ceil(T / 2) times.  Graph
-        replay as in decode(), keyed (bs, T, mode), on static buffers of its own."""
-        tp.check_comm()
-        assert tokens.dim() == 2 and tokens.dtype == torch.int64
-        bs, T = tokens.shape
-        if T == 1:
-            raise ValueError("decode_multi is the multi-token step (T > 1); decode() is the single-token one")
-        if T > MLA_MULTI_MAX_Q:
-            raise ValueError(f"decode_multi: {T} tokens per sequence; 2 .. {MLA_MULTI_MAX_Q} are implemented")
-        _check_multi_step_rows(bs * T)
-        flat = tokens.reshape(bs * T)
-        if not use_graph or tp.xgmi_split_phase():
-            return self.decode_eager(flat, T).view(bs, T, -1)
-        mode = graphs.graph_mode(use_graph)
-        key, skey = (bs, T, mode), (bs, T)
-        if skey not in self.static_tokens:
-            self.static_tokens[skey] = flat.clone()
-        else:
-            self.static_tokens[skey].copy_(flat)
-        if key not in self.graphs:
-            g, self.graph_pool, self.static_out[skey] = graphs.capture_verified(
-                lambda: self.decode_eager(self.static_tokens[skey], T), self.static_out.get(skey), mode, self.graph_pool,
-                what=f"DeepSeekV3Decoder multi-token decode step bs={bs} T={T}")
-            self.graphs[key] = g
-        self.graphs[key].replay()
-        return self.static_out[skey].view(bs, T, -1)
-
-    @torch.inference_mode()
-    def generate_speculative(self, prompts, max_new_tokens, drafter, draft_len, req_ids=None, use_graph=True, temperatures=None,
-                             top_ks=None, top_ps=None, frequency_penalties=None, generator=None):
-        """Greedy generation with draft-and-verify, LlamaDecoder.generate_speculative's contract on decode_multi: the tokens
-        plain greedy generate() picks, in fewer steps when the drafter is right (drafter.propose(history, draft_len); a
-        DeepSeek-V3 checkpoint's multi-token-prediction head is such a drafter, chitu_amd.sampling.NgramDrafter another).
-        Returns [n_req, max_new_tokens] int64 and frees the requests' pages; self.speculative_stats = {"steps", "accepted",
-        "drafted"}.  Greedy only: any sampling argument raises (generate_speculative_sampled takes them); draft_len outside 1 .. 7 raises."""
-        from . import sampling
-
-        return sampling.generate_speculative_greedy(self, prompts, max_new_tokens, drafter, draft_len, MLA_MULTI_MAX_Q, req_ids, use_graph,
-                                                    (temperatures, top_ks, top_ps, frequency_penalties, generator))
-
-    @torch.inference_mode()
-    def generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, temperatures=None, top_ks=None, top_ps=None,
-                                     frequency_penalties=None, generator=None, req_ids=None, use_graph=True):
-        """generate_speculative with generate()'s sampling parameters, LlamaDecoder.generate_speculative_sampled's contract on
-        this decoder's decode_multi: one chitu_hip_speculative_verify call per round accepts a draft d with probability p(d)
-        under the distribution p generate()'s sampler draws from, and replaces the first rejected draft by a draw from p without
-        d, renormalised.  A drafter with propose(history, k) is a deterministic proposal; a sampling.ModelDrafter drafts on the
-        device with a draft model (e.g. a shallow stack of this decoder) and, with sample=True, draws its drafts from its own
-        distribution q under the request's parameters and hands over its logits: chitu_hip_speculative_verify_sampled accepts
-        with min(1, p(d) / q(d)) and replaces from max(p - q, 0), lossless for any q that d was drawn from (the drafter samples
-        without the frequency penalty).  The output tokens are distributed as generate()'s but come from another
-        uniform stream.  With every top_k <= 1 the result is generate_speculative's."""
-        from . import sampling
-
-        return sampling.generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, MLA_MULTI_MAX_Q, temperatures,
-                                                     top_ks, top_ps, frequency_penalties, generator, req_ids, use_graph)
+    def check_step(self, kind, rows=0):
+        if kind == "multi-token decode":
+            _check_multi_step_rows(rows)
 
 
 def _check_multi_step_rows(rows: int):

@@ -17,12 +17,12 @@ from dataclasses import dataclass
 from typing import Optional
 
 import torch
-import torch.nn.functional as F
 
-from . import graphs, ops
+from . import ops
 from . import tensor_parallel as tp
 from .attn_backend import GQA_MULTI_MAX_Q, HipAttnBackend
 from .cache_manager import PagedKVCacheManager, gqa_kv_layout
+from .decoder import DecoderBase
 
 
 @dataclass
@@ -278,30 +278,43 @@ class LlamaFeedForward(torch.nn.Module):
         return ops.bf16_linear(ops.bf16_linear_silu(x, self.w13), self.w2)
 
 
-class LlamaBlock(torch.nn.Module):
-    rotary_type = "llama"  # subclasses (Qwen3) name the half-split layout
+class GqaBlock(torch.nn.Module):
+    """A LlamaAttention behind attn_norm and an FFN behind ffn_norm; the residual adds are folded into the RMSNorm that consumes
+    them.  The attention half is stated here once; a family names its FFN module and states the FFN half in forward()."""
+
+    rotary_type = "llama"  # subclasses name the half-split ("hf-llama": Qwen, Mixtral) or the partial ("glm4") layout
+    ffn_type = None  # the module behind ffn_norm: ffn_type(args, device)
 
     def __init__(self, layer_id, args, cache, attn_backend, device=None):
         super().__init__()
         self.attn = LlamaAttention(args, layer_id, cache, attn_backend, device, rotary_type=self.rotary_type)
-        self.ffn = LlamaFeedForward(args, device)
+        self.ffn = self.ffn_type(args, device)
         self.attn_norm = _param(args.dim, device=device)
         self.ffn_norm = _param(args.dim, device=device)
         self.eps = args.norm_eps
 
-    def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
-        """(x, pending) -> (x', pending'): residual adds folded into the RMSNorm that consumes them;
-        varlens given = prefill; q_len > 1: the rows are q_len tokens per sequence (LlamaDecoder.decode_multi)."""
-        if varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0], weight=self.attn.wqkv):
-            # small decode batches: the add + norm run as the prologue of the projection that consumes them
+    def attn_part(self, x, pending, cos, sin, varlens, q_len, fuse=True, **fuses_norm_args):
+        """(x, pending) -> (x + pending, the attention's output with its all-reduce deferred).  Small decode batches
+        (_fuses_norm, with the block's own arguments; fuse=False: never): the add + attn_norm run as the prologue of the qkv
+        projection, bit-identical, one launch less per layer.  varlens given = prefill."""
+        if fuse and varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0], **fuses_norm_args):
             x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin, q_len)
-            a = tp.defer_all_reduce(a)
         else:
             x, hn = tp.add_norm(x, pending, self.attn_norm, self.eps)[:2]
             if varlens is None:
-                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin, q_len))
+                a = self.attn.decode_forward_paged(hn, cos, sin, q_len)
             else:
-                a = tp.defer_all_reduce(self.attn.prefill_forward(hn, cos, sin, varlens))
+                a = self.attn.prefill_forward(hn, cos, sin, varlens)
+        return x, tp.defer_all_reduce(a)
+
+
+class LlamaBlock(GqaBlock):
+    ffn_type = LlamaFeedForward
+
+    def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
+        """(x, pending) -> (x', pending'); varlens given = prefill; q_len > 1: the rows are q_len tokens per sequence
+        (DecoderBase.decode_multi)."""
+        x, a = self.attn_part(x, pending, cos, sin, varlens, q_len, weight=self.attn.wqkv)
         return self.ffn_part(x, a, varlens)
 
     def ffn_part(self, x, a, varlens):
@@ -312,15 +325,15 @@ class LlamaBlock(torch.nn.Module):
         return x, tp.defer_all_reduce(self.ffn(hn))
 
 
-class LlamaDecoder(torch.nn.Module):
-    """embed -> blocks -> norm -> head -> fp32 logits; one hipGraph per batch size (model.py:538-622)."""
+class LlamaDecoder(DecoderBase):
+    """DecoderBase over GQA blocks with bf16 (or W8A16) linears and a paged K / V cache (model.py:538-622)."""
 
     block_type = None  # subclasses (Mixtral) swap the block
+    multi_max_q = GQA_MULTI_MAX_Q
 
     def __init__(self, args: LlamaArgs, cache: PagedKVCacheManager, attn_backend: HipAttnBackend,
                  max_position_embeddings: int = 4096, device="cuda"):
-        super().__init__()
-        self.args, self.cache, self.attn_backend, self.device = args, cache, attn_backend, torch.device(device)
+        super().__init__(args, cache, attn_backend, device)
         t = tp.get_tp_size()
         check_quant_supported(getattr(args, "quant", None), type(self).__name__)
         assert args.vocab_size % t == 0 and args.n_kv_heads % t == 0 and args.head_dim == 128, "gqa_decode: head_dim 128"
@@ -345,233 +358,15 @@ class LlamaDecoder(torch.nn.Module):
         # rotary_dim: the channels of a head that rotate (GLM-4: 64 of 128); every other model has no such field
         cos, sin = precompute_freqs_cis(getattr(args, "rotary_dim", args.head_dim), max_position_embeddings, args.rope_theta)
         self.cos_table, self.sin_table = cos.to(device), sin.to(device)
-        self.graphs, self.static_tokens, self.static_out = {}, {}, {}
-        self.graph_pool = None
 
-    def embed(self, tokens):
-        if self.vocab_local == self.args.vocab_size:
-            return F.embedding(tokens, self.embed_weight)
-        local = tokens - self.vocab_start
-        mask = (local < 0) | (local >= self.vocab_local)
-        y = F.embedding(torch.where(mask, torch.zeros_like(local), local), self.embed_weight)
-        return tp.all_reduce(torch.where(mask.unsqueeze(-1), torch.zeros_like(y), y))
+    def final_norm(self):
+        return self.norm, self.args.norm_eps
 
-    @torch.inference_mode()
-    def prefill(self, tokens, req_ids, chunk_size=None):
-        """Ragged prompts -> fp32 logits [n_req, vocab] of each prompt's last token; fills the KV pages
-        (prefill_single_device, model.py:451-465).  chunk_size = c: the first c tokens of every prompt run here, the rest in
-        rounds of prefill_continue with at most c tokens per request (a request whose prompt is exhausted leaves the later
-        rounds), so no round holds more than n_req * c rows.  An fp8 K / V cache raises NotImplementedError first."""
-        from .deepseek_v3 import VarLens
-
-        if chunk_size is not None:
-            c = int(chunk_size)
-            if c < 1:
-                raise ValueError(f"chunk_size={chunk_size}: at least one token per round")
-            if self.args.kv_cache_dtype == "fp8":
-                raise NotImplementedError("chunked prefill attends over bf16 K / V pages; kv_cache_dtype='fp8' is not implemented")
-            req_ids = list(req_ids)
-            logits = self.prefill([list(t[:c]) for t in tokens], req_ids)
-            done = c
-            while True:
-                live = [i for i, t in enumerate(tokens) if len(t) > done]
-                if not live:
-                    return logits
-                out = self.prefill_continue([list(tokens[i][done : done + c]) for i in live], [req_ids[i] for i in live])
-                logits[torch.tensor(live, device=logits.device)] = out  # a later round overwrites it until the prompt ends
-                done += c
-
-        from . import graphs
-
-        graphs.sweep_if_memory_was_recycled()  # the eager path's canary: once after an xGMI communicator came or went
-        varlens = VarLens(tokens, self.device)
-        self.cache.curr_varlens, self.cache.curr_req_ids = varlens, list(req_ids)
-        flat = torch.tensor([t for seq in tokens for t in seq], dtype=torch.int64, device=self.device)
-        cos, sin = self.cos_table[varlens.position_ids], self.sin_table[varlens.position_ids]
-        h, pending = self.embed(flat), None
-        for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin, varlens)
-        last = torch.tensor([p - 1 for p in varlens.cpu_prefix_lens[1:]], dtype=torch.int64, device=self.device)
-        h = ops.rms_norm(h[last], self.norm, self.args.norm_eps, add=tp.resolve(pending)[last].contiguous())[1]
-        self.cache.finalize_cache_all_prefill(req_ids, varlens)
-        return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight)).float()
-
-    @torch.inference_mode()
-    def prefill_continue(self, tokens, req_ids):
-        """Ragged chunks of new tokens for requests that are already cached (a conversation's next turn, the next chunk of a
-        long prompt, a draft model's catch-up) -> fp32 logits [n_req, vocab] of each chunk's last token; appends their K / V
-        rows.  Positions, and so cos / sin, continue from each request's cached length.  The attention reads the pages
-        (LlamaAttention.prefill_forward_paged); everything else is prefill's stack on the new rows.  kv_cache_dtype="fp8"
-        raises NotImplementedError before anything changes."""
-        from .deepseek_v3 import VarLens
-
-        from . import graphs
-
-        if self.args.kv_cache_dtype == "fp8":
-            raise NotImplementedError("continued prefill attends over bf16 K / V pages; kv_cache_dtype='fp8' is not implemented")
-        req_ids = list(req_ids)
-        assert len(tokens) == len(req_ids) and all(len(t) >= 1 for t in tokens)
-        for r, t in zip(req_ids, tokens):
-            assert self.cache.seq_lens[r] + len(t) <= self.cos_table.shape[0], \
-                f"request {r!r}: {self.cache.seq_lens[r]} + {len(t)} tokens exceed max_position_embeddings={self.cos_table.shape[0]}"
-        graphs.sweep_if_memory_was_recycled()
-        varlens = VarLens(tokens, self.device)
-        varlens.continued = True
-        self.cache.prepare_cache_prefill_continue(req_ids, varlens)
-        pos = self.cache.get_continue_position_ids()
-        flat = torch.tensor([t for seq in tokens for t in seq], dtype=torch.int64, device=self.device)
-        cos, sin = self.cos_table[pos], self.sin_table[pos]
-        h, pending = self.embed(flat), None
-        for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin, varlens)
-        last = torch.tensor([p - 1 for p in varlens.cpu_prefix_lens[1:]], dtype=torch.int64, device=self.device)
-        h = ops.rms_norm(h[last], self.norm, self.args.norm_eps, add=tp.resolve(pending)[last].contiguous())[1]
-        self.cache.finalize_cache_all_prefill_continue(req_ids)
-        return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight)).float()
-
-    @torch.inference_mode()
-    def generate(self, prompts, max_new_tokens, req_ids=None, use_graph=True, temperatures=None, top_ks=None,
-                 top_ps=None, frequency_penalties=None, generator=None, prefill_chunk_size=None):
-        """Prefill (prefill_chunk_size: in chunks, prefill's chunk_size), then max_new_tokens - 1 decode steps; returns [n_req, max_new_tokens] int64 and frees the
-        requests' pages.  Token selection is executor.py:82-112 on the device (chitu_amd.sampling): greedy
-        unless some top_k > 1 (then per-request temperature / top-k / top-p sampling, uniforms from
-        `generator`), with an optional per-request frequency penalty; tokens never visit the host."""
-        from .sampling import DeviceSampler
-
-        req_ids = [f"gen{i}" for i in range(len(prompts))] if req_ids is None else list(req_ids)
-        pick = DeviceSampler(len(prompts), max_new_tokens, self.device, temperatures, top_ks, top_ps,
-                             frequency_penalties, generator)
-        tok = pick(self.prefill(prompts, req_ids) if prefill_chunk_size is None else
-                   self.prefill(prompts, req_ids, chunk_size=prefill_chunk_size))
-        out = [tok]
-        for _ in range(max_new_tokens - 1):
-            self.cache.prepare_cache_decode(req_ids)
-            self.cache.prepare_block_table_for_decode(req_ids)
-            tok = pick(self.decode(tok, use_graph=use_graph))
-            self.cache.finalize_cache_single_decode(req_ids)
-            out.append(tok)
-        for r in req_ids:
-            self.cache.finalize_cache_all_decode(r)
-        tokens_out = torch.stack(out, dim=1)
-        if tp.xgmi_comm() is not None:
-            # the tokens are about to leave the engine: make sure no collective behind them gave up on a peer
-            torch.cuda.current_stream().synchronize()
-            tp.check_comm()
-        return tokens_out
-
-    def decode_eager(self, tokens, q_len=1):
-        """tokens [rows] int64.  q_len > 1: rows = q_len consecutive tokens of each sequence, positions and page rows from the
-        cache manager's multi-token buffers."""
-        # embedding rows of this rank's vocabulary slice + every row's rotary row: one launch
-        positions = self.cache.get_gpu_multi_row_lens() if q_len > 1 else self.cache.get_gpu_seq_lens_excl_this_decode()
-        h, cos, sin = ops.embed_rope_gather(tokens, self.embed_weight, self.vocab_start if self.vocab_local != self.args.vocab_size else 0,
-                                            positions, self.cos_table, self.sin_table)
-        if self.vocab_local != self.args.vocab_size:
-            h = tp.all_reduce(h)
-        pending = None
-        for layer in self.layers:
-            h, pending = layer(h, pending, cos, sin, q_len=q_len)
-        h = tp.add_norm(h, pending, self.norm, self.args.norm_eps)[1]
-        return tp.all_gather_last_dim(ops.bf16_linear(h, self.head_weight), out_dtype=torch.float32)
-
-    @torch.inference_mode()
-    def decode(self, tokens, use_graph=True):
-        """Eager, or the step captured per batch size: one hipGraph, or -- on a rank with collectives --
-        hipGraph pieces with the collectives between them (chitu_amd/graphs.py)."""
-        tp.check_comm()  # a collective of an earlier step that timed out: raise instead of decoding garbage
-        bs = tokens.shape[0]
-        if not use_graph or tp.xgmi_split_phase():  # (split-phase collectives hold a host barrier: not capturable)
-            return self.decode_eager(tokens)
-        mode = graphs.graph_mode(use_graph)
-        key = (bs, mode)
-        if bs not in self.static_tokens:
-            self.static_tokens[bs] = tokens.clone()
-        else:
-            self.static_tokens[bs].copy_(tokens)
-        if key not in self.graphs:
-            # eager step on the static inputs (also re-writes this step's KV rows), capture, ONE checked replay
-            g, self.graph_pool, self.static_out[bs] = graphs.capture_verified(
-                lambda: self.decode_eager(self.static_tokens[bs]), self.static_out.get(bs), mode, self.graph_pool,
-                what=f"{type(self).__name__} decode step bs={bs}")
-            self.graphs[key] = g
-        self.graphs[key].replay()
-        return self.static_out[bs]
-
-    @torch.inference_mode()
-    def decode_multi(self, tokens, use_graph=True):
-        """One step over T = tokens.shape[1] tokens per sequence (1 < T <= 8): tokens [bs, T] int64 are appended at each
-        sequence's length .. + T - 1 and token t attends to everything up to itself -- the verify step of speculative decoding.
-        Returns fp32 logits [bs, T, vocab]: row (b, t) predicts the token after tokens[b, t].  The caller has run
-        cache.prepare_block_table_for_decode_multi(req_ids, T) and settles the lengths with finalize_cache_multi_decode.
-
-        The stack runs on bs * T rows (embedding, norms, GEMMs and the RoPE + append launch take per-row positions; the fused
-        small-batch launches apply by their row limits on bs * T); only the attention call knows T.  Graph replay as in decode(),
-        keyed (bs, T, mode), on static buffers of its own."""
-        tp.check_comm()
-        assert tokens.dim() == 2 and tokens.dtype == torch.int64
-        bs, T = tokens.shape
-        if T == 1:
-            raise ValueError("decode_multi is the multi-token step (T > 1); decode() is the single-token one")
-        flat = tokens.reshape(bs * T)
-        if not use_graph or tp.xgmi_split_phase():
-            return self.decode_eager(flat, T).view(bs, T, -1)
-        mode = graphs.graph_mode(use_graph)
-        key, skey = (bs, T, mode), (bs, T)
-        if skey not in self.static_tokens:
-            self.static_tokens[skey] = flat.clone()
-        else:
-            self.static_tokens[skey].copy_(flat)
-        if key not in self.graphs:
-            g, self.graph_pool, self.static_out[skey] = graphs.capture_verified(
-                lambda: self.decode_eager(self.static_tokens[skey], T), self.static_out.get(skey), mode, self.graph_pool,
-                what=f"{type(self).__name__} multi-token decode step bs={bs} T={T}")
-            self.graphs[key] = g
-        self.graphs[key].replay()
-        return self.static_out[skey].view(bs, T, -1)
-
-    @torch.inference_mode()
-    def generate_speculative(self, prompts, max_new_tokens, drafter, draft_len, req_ids=None, use_graph=True, temperatures=None,
-                             top_ks=None, top_ps=None, frequency_penalties=None, generator=None):
-        """Greedy generation with draft-and-verify: the tokens plain greedy generate() picks, in fewer steps when the drafter is
-        right.  Each round, drafter.propose(history, draft_len) names draft_len tokens per request (history = prompt + tokens
-        so far), ONE decode_multi step runs over [last token | drafts], the longest prefix with draft[i] == argmax(logits[i]) is
-        accepted, the argmax at the first mismatch (or after the last draft) is emitted as the bonus token, and the cache
-        keeps accepted + 1 rows.  A request leaves the batch when it has max_new_tokens.  Returns [n_req, max_new_tokens] int64
-        and frees the requests' pages; self.speculative_stats = {"steps": verify steps run, "accepted": drafts accepted,
-        "drafted": drafts proposed}.  Greedy only: any sampling argument raises (generate_speculative_sampled takes them).  The drafter runs on the host: the accepted
-        counts have to reach the host for the page accounting anyway (one small copy per round).  Every request needs room
-        for draft_len tokens beyond prompt + max_new_tokens in its block table."""
-        from . import sampling
-
-        return sampling.generate_speculative_greedy(self, prompts, max_new_tokens, drafter, draft_len, GQA_MULTI_MAX_Q, req_ids, use_graph,
-                                                    (temperatures, top_ks, top_ps, frequency_penalties, generator))
-
-    @torch.inference_mode()
-    def generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, temperatures=None, top_ks=None, top_ps=None,
-                                     frequency_penalties=None, generator=None, req_ids=None, use_graph=True):
-        """generate_speculative's draft-and-verify loop with generate()'s sampling parameters (per request: temperature, top_k,
-        top_p, frequency penalty; `generator`: a CUDA torch.Generator for the uniforms).  The first token is sampled from the
-        prefill logits.  Each round ONE decode_multi step runs over [last token | drafts] and ONE chitu_hip_speculative_verify
-        call judges the drafts on the device: under the distribution p that generate()'s sampler draws from for the row, a
-        draft d is accepted with probability p(d); the first rejected draft is replaced by a draw from p without d,
-        renormalised; after draft_len accepted drafts a bonus token is drawn from p.  The frequency penalty of row t counts the
-        response so far and the round's drafts before t.
-
-        A drafter with propose(history, draft_len) names tokens: a deterministic proposal, and the rule above is rejection
-        sampling against a point mass.  A sampling.ModelDrafter drafts on the device with a draft model and, with sample=True,
-        draws each draft from the draft model's distribution q under the request's own temperature / top_k / top_p (without the
-        frequency penalty) and hands over its logits: ONE chitu_hip_speculative_verify_sampled call accepts d with min(1, p(d) /
-        q(d)) and replaces a rejected draft by a draw from max(p - q, 0), renormalised -- lossless for any q, provided q is what
-        d was drawn from.  The output tokens are distributed as
-        generate()'s with the same parameters, but they come from another uniform stream: the same generator seed does not
-        give generate()'s tokens.  With every top_k <= 1 the result is generate_speculative's.
-
-        Returns [n_req, max_new_tokens] int64, frees the requests' pages, leaves self.speculative_stats as generate_speculative
-        does.  draft_len outside 1 .. 7 raises."""
-        from . import sampling
-
-        return sampling.generate_speculative_sampled(self, prompts, max_new_tokens, drafter, draft_len, GQA_MULTI_MAX_Q, temperatures,
-                                                     top_ks, top_ps, frequency_penalties, generator, req_ids, use_graph)
+    def check_step(self, kind, rows=0):
+        """Chunked and continued prefill attend over bf16 K / V pages (LlamaAttention.prefill_forward_paged).  A multi-token step
+        of more rows than the xGMI communicator holds is not refused: its collectives take the library path."""
+        if kind != "multi-token decode" and self.args.kv_cache_dtype == "fp8":
+            raise NotImplementedError(f"{kind} attends over bf16 K / V pages; kv_cache_dtype='fp8' is not implemented")
 
 
 @torch.no_grad()

@@ -16,7 +16,7 @@ import torch
 from . import fused_moe, ops
 from . import tensor_parallel as tp
 from .deepseek_v3 import _route_align_enabled
-from .llama import LlamaAttention, LlamaDecoder, _fuses_norm, _param
+from .llama import GqaBlock, LlamaDecoder, _param
 
 
 @dataclass
@@ -80,27 +80,13 @@ class MixtralSparseMoe(torch.nn.Module):
                                        reduce_topk=not defer_sum)
 
 
-class MixtralBlock(torch.nn.Module):
-    def __init__(self, layer_id, args, cache, attn_backend, device=None):
-        super().__init__()
-        self.attn = LlamaAttention(args, layer_id, cache, attn_backend, device, rotary_type="hf-llama")
-        self.ffn = MixtralSparseMoe(args, device)
-        self.attn_norm = _param(args.dim, device=device)
-        self.ffn_norm = _param(args.dim, device=device)
-        self.eps = args.norm_eps
+class MixtralBlock(GqaBlock):
+    rotary_type = "hf-llama"
+    ffn_type = MixtralSparseMoe
 
     def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
-        if FUSE and varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0], two_terms_ok=self.attn.rotary_type != "llama"):
-            # small decode batches: residual add + attn_norm run as the prologue of the qkv projection (round 6: the Llama
-            # blocks' fusion, bit-identical, one launch less per layer)
-            x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin, q_len)
-            a = tp.defer_all_reduce(a)
-        else:
-            x, hn = tp.add_norm(x, pending, self.attn_norm, self.eps)[:2]
-            if varlens is None:
-                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin, q_len))
-            else:
-                a = tp.defer_all_reduce(self.attn.prefill_forward(hn, cos, sin, varlens))
+        # the prologue of the qkv projection (round 6) also takes the experts' un-summed top-2 outputs
+        x, a = self.attn_part(x, pending, cos, sin, varlens, q_len, fuse=FUSE, two_terms_ok=self.attn.rotary_type != "llama")
         # ffn_norm with the experts' per-token int8 quantisation of its output in the same launch (round 6: quant_act's arithmetic
         # on the same bf16 values, bit-identical codes; decode only -- prefill keeps the separate launch over thousands of rows)
         if FUSE and varlens is None and x.is_cuda:

@@ -19,7 +19,7 @@ import torch
 from . import fused_moe, ops
 from . import tensor_parallel as tp
 from .deepseek_v3 import _route_align_enabled
-from .llama import LlamaAttention, LlamaDecoder, _fuses_norm, _param
+from .llama import GqaBlock, LlamaDecoder, _param
 
 # Prompt tokens from which the experts take the tiled grouped GEMMs (0 = never; fused_moe._takes_tiled's per-expert floor
 # applies as well: 24 slots per expert, i.e. 384 tokens at 128 experts / top 8).  Measured on an MI355X at Qwen3-30B-A3B's shapes
@@ -107,27 +107,14 @@ class Qwen3MoeSparseMoe(torch.nn.Module):
                                        bf16_tiled_min_tokens=self.tiled_min_tokens)
 
 
-class Qwen3MoeBlock(torch.nn.Module):
-    def __init__(self, layer_id, args, cache, attn_backend, device=None):
-        super().__init__()
-        self.attn = LlamaAttention(args, layer_id, cache, attn_backend, device, rotary_type="hf-llama")
-        self.ffn = Qwen3MoeSparseMoe(args, device)
-        self.attn_norm = _param(args.dim, device=device)
-        self.ffn_norm = _param(args.dim, device=device)
-        self.eps = args.norm_eps
+class Qwen3MoeBlock(GqaBlock):
+    rotary_type = "hf-llama"
+    ffn_type = Qwen3MoeSparseMoe
 
     def forward(self, x, pending, cos, sin, varlens=None, q_len=1):
-        if varlens is None and _fuses_norm(x, pending, self.attn.wqkv.shape[0]):
-            # small decode batches, summed pending: residual add + attn_norm run as the prologue of the qkv projection (LlamaBlock's
-            # fusion; un-summed expert outputs take the norm launch below, which sums up to 16 terms)
-            x, a = self.attn.decode_from_residual(x, pending, self.attn_norm, self.eps, cos, sin, q_len)
-            a = tp.defer_all_reduce(a)
-        else:
-            x, hn = tp.add_norm(x, pending, self.attn_norm, self.eps)[:2]
-            if varlens is None:
-                a = tp.defer_all_reduce(self.attn.decode_forward_paged(hn, cos, sin, q_len))
-            else:
-                a = tp.defer_all_reduce(self.attn.prefill_forward(hn, cos, sin, varlens))
+        # the prologue of the qkv projection takes a summed pending only: un-summed expert outputs go to the norm launch, which
+        # sums up to 16 terms
+        x, a = self.attn_part(x, pending, cos, sin, varlens, q_len)
         x, hn = tp.add_norm(x, a, self.ffn_norm, self.eps)[:2]
         # decode: the top-k sum moves into the next residual add whenever nothing else needs the summed tensor
         defer = varlens is None and x.is_cuda and tp.defers_topk_sum(hn.shape[0], hn.shape[1], self.ffn.topk)
