@@ -4,8 +4,15 @@ Reference (read-only): chitu/fused_moe.py -- moe_align_block_size:599-610 (+ _cu
 _native:522-596), per_token_group_quant_fp8:713-793, fused_experts:1060-1127,
 fused_experts_impl:1130-1307, SiluAndMul:24-39.  No Triton here: every step is a hand-written
 HIP kernel behind libchitu_hip.so, and there is no fallback path.
+
+fused_experts has one host routine per expert format -- fp8 W8A8 (`fused_experts_impl`), MXFP4 W4A8 (`_fused_experts_mxfp4`),
+int8 W8A8 (`_fused_experts_int8`), bf16 activations over bf16 or soft-fp8 experts (`_fused_experts_bf16_act`) -- and each holds
+only what is its own: the weight and scale checks, the scratch list, the activation quantiser and the GEMM launches.
+Everything else (sizes, `out`, the empty batch, the tiled-or-streaming decision through `_takes_tiled`, the workspace
+carve-up, the align launch or the caller's `aligned`, the top-k sum or the `reduce_topk=False` view) is `_MoePlan`.
 """
 
+import ctypes
 import os
 from typing import List, Optional, Tuple
 
@@ -172,6 +179,92 @@ def _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, min_to
     return (_MOE_TILED_MIN_TOKENS > 0 and floor > 0 and num_tokens >= floor and aligned is None and I % 128 == 0
             and Nout % 8 == 0 and numel >= _MOE_TILED_MIN_PER_EXPERT * global_num_experts)
 
+
+class _MoePlan:
+    """What one fused_experts call does whatever the experts' format: the sizes, `out`, the streaming-or-tiled decision, the
+    carve-up of the persistent "moe" workspace, the sorted routing and the tail.  A format's routine makes its weight checks,
+    then
+
+        p = _MoePlan(...)                 # sizes, out, contiguous top-k tensors, tiled / block_m / cap / nblk: no library call
+        if p.num_tokens == 0: return p.out
+        sorted_p, experts_p, npost_p = p.align([(name, bytes), ...], expert_map)   # workspace + one align launch (or `aligned`)
+        ... its quantiser and GEMM launches on p.P(name); the last one writes [numel, Nout] bf16 into "c3" ...
+        return p.finish()                 # the top-k sum into out, or the view of "c3"
+
+    tiles=False: the format has no tiled form, `_takes_tiled` is not asked.  min_tokens: the format's floor for `_takes_tiled`."""
+
+    def __init__(self, hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, aligned, reduce_topk,
+                 tiles=True, min_tokens=None):
+        self.num_tokens, self.K = hidden_states.shape
+        self.E, self.N = w1.shape[0], w1.shape[1]
+        self.I = self.N // 2
+        self.Nout = w2.shape[1]
+        self.topk = topk_ids.shape[1]
+        self.numel = self.num_tokens * self.topk
+        self.global_num_experts = self.E if global_num_experts == -1 else global_num_experts
+        self.dev = hidden_states.device
+        self.out = hidden_states if inplace else torch.empty_like(hidden_states)
+        self.reduce_topk = reduce_topk
+        self.aligned = aligned
+        if self.num_tokens == 0:
+            return
+        assert self.Nout == self.K or not reduce_topk, "the summed output has the hidden size"  # moe_sum writes Nout columns into out
+        self.topk_ids = topk_ids.contiguous()
+        self.topk_weights = topk_weights.contiguous()
+        self.tiled = tiles and _takes_tiled(self.num_tokens, self.numel, self.global_num_experts, self.I, self.Nout, aligned,
+                                            min_tokens=min_tokens)
+        self.block_m = _MOE_TILED_BLOCK_M if self.tiled else _MOE_BLOCK_M
+        self.cap = self.numel + self.global_num_experts * (self.block_m - 1)
+        self.nblk = ceil_div(self.cap, self.block_m)
+        assert not self.tiled or self.nblk <= 65535  # the tiled kernels' grid
+        self.max_mblocks = min(self.nblk, self.numel)
+        self.lib, self.st = _lib.lib(), stream_ptr()
+
+    def P(self, name):
+        return ctypes.c_void_p(self.base + self.off[name])
+
+    def align(self, scratch, expert_map):
+        """Carve "sorted", "experts", "npost", "cumsum" and then the format's `scratch` [(name, bytes) ...] out of the
+        workspace at 256-byte steps, and sort the routing: one launch, or the caller's `aligned` triple, which must be what
+        moe_align_block_size(topk_ids, 16, global_num_experts, expert_map) returns.  -> the three pointers."""
+        sizes = [("sorted", self.cap * 4), ("experts", self.nblk * 4), ("npost", 4),
+                 ("cumsum", (self.global_num_experts + 1) * 4)] + scratch
+        self.off, cur = {}, 0
+        for name, n in sizes:
+            self.off[name] = cur
+            cur += (n + 255) // 256 * 256
+        self.ws = workspace.get(cur, self.dev, "moe")
+        self.base = self.ws.data_ptr()
+        P = self.P
+        if self.aligned is None:
+            emap = _expert_map_i32(expert_map, self.global_num_experts, self.dev)
+            check(
+                self.lib.chitu_hip_moe_align_block_size_mapped(
+                    ptr(self.topk_ids), int_dtype_code(self.topk_ids.dtype), i64(self.numel), i32(self.global_num_experts),
+                    i32(self.block_m), P("sorted"), i64(self.cap), P("experts"), i64(self.nblk), P("npost"), P("cumsum"),
+                    i32(1), ptr(emap), self.st,
+                ),
+                "moe_align_block_size",
+            )
+            return P("sorted"), P("experts"), P("npost")
+        # the router's launch already sorted the ids (ops.gate_deepseek_v3(align=...)): one launch less per layer
+        a_sorted, a_experts, a_npost = self.aligned
+        require_cuda(a_sorted, a_experts, a_npost)
+        assert a_sorted.dtype == torch.int32 and a_experts.dtype == torch.int32 and a_npost.dtype == torch.int32
+        assert a_sorted.numel() == self.cap and a_experts.numel() == self.nblk, "aligned buffers must come from block 16 over global_num_experts"
+        return ptr(a_sorted), ptr(a_experts), ptr(a_npost)
+
+    def finish(self):
+        """reduce_topk: out[t] = sum over the token's top-k rows of "c3".  Otherwise those rows themselves, [tokens, topk,
+        Nout]: a view of the workspace, valid until the next fused_experts call."""
+        if not self.reduce_topk:
+            c3 = self.off["c3"]
+            return self.ws[c3 : c3 + self.numel * self.Nout * 2].view(torch.bfloat16).view(self.num_tokens, self.topk, self.Nout)
+        check(self.lib.chitu_hip_moe_sum(self.P("c3"), ptr(self.out), i64(self.num_tokens), i32(self.topk), i64(self.Nout),
+                                         self.st), "moe sum")
+        return self.out
+
+
 class SiluAndMul(torch.nn.Module):
     """x -> silu(x[..., :d]) * x[..., d:]  (chitu/fused_moe.py:24-39).  Kept for API parity; the
     fused path applies it inside chitu_hip_moe_silu_mul_quant_fp8."""
@@ -302,91 +395,22 @@ def fused_experts_impl(
     require_cuda(hidden_states, w1, w2, topk_weights, topk_ids, w1_scale, w2_scale)
     assert w1_scale.is_contiguous() and w2_scale.is_contiguous()
     assert w1_scale.dtype == torch.float32 and w2_scale.dtype == torch.float32
+    assert w2.shape[0] == w1.shape[0] and w2.shape[2] == w1.shape[1] // 2, "w2 must be [E, hidden_out, N/2]"
 
-    num_tokens, K = hidden_states.shape
-    E, N, _ = w1.shape
-    I = N // 2
-    assert w2.shape[0] == E and w2.shape[2] == I, "w2 must be [E, hidden_out, N/2]"
-    Nout = w2.shape[1]
-    if global_num_experts == -1:
-        global_num_experts = E
-    topk = topk_ids.shape[1]
-    dev = hidden_states.device
-    out = hidden_states if inplace else torch.empty_like(hidden_states)
-    if num_tokens == 0:
-        return out
-    numel = num_tokens * topk
-    if not topk_ids.is_contiguous():
-        topk_ids = topk_ids.contiguous()
-    if not topk_weights.is_contiguous():
-        topk_weights = topk_weights.contiguous()
-
-    # ---- scratch carve-up (persistent, 256-B aligned)
-    def rnd(n):
-        return (n + 255) // 256 * 256
-
-    tiled = _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned)
-    block_m = _MOE_TILED_BLOCK_M if tiled else _MOE_BLOCK_M
-    cap = numel + global_num_experts * (block_m - 1)
-    nblk = ceil_div(cap, block_m)
-    KB = K // 128
-    sizes = [
-        ("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
-        ("a1q", num_tokens * K), ("a1s", num_tokens * KB * 4), ("c1", numel * N * 2),
-        ("a2q", numel * I), ("a2s", numel * (I // 128) * 4), ("c3", numel * Nout * 2),
-    ]
-    total = sum(rnd(n) for _, n in sizes)
-    ws = workspace.get(total, dev, "moe")
-    base = ws.data_ptr()
-    off = {}
-    cur = 0
-    for name, n in sizes:
-        off[name] = base + cur
-        cur += rnd(n)
-    import ctypes as _ct
-
-    P = lambda name: _ct.c_void_p(off[name])
-    lib = _lib.lib()
-    st = stream_ptr()
-    max_mblocks = min(nblk, numel)
-
-    if aligned is None:
-        emap = _expert_map_i32(expert_map, global_num_experts, dev)
-        check(
-            lib.chitu_hip_moe_align_block_size_mapped(
-                ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel), i32(global_num_experts),
-                i32(block_m), P("sorted"), i64(cap), P("experts"), i64(nblk), P("npost"), P("cumsum"),
-                i32(1), ptr(emap), st,
-            ),
-            "moe_align_block_size",
-        )
-        sorted_p, experts_ptr, npost_p = P("sorted"), P("experts"), P("npost")
-    else:
-        a_sorted, a_experts, a_npost = aligned
-        require_cuda(a_sorted, a_experts, a_npost)
-        assert a_sorted.dtype == torch.int32 and a_experts.dtype == torch.int32 and a_npost.dtype == torch.int32
-        assert a_sorted.numel() == cap and a_experts.numel() == nblk, "aligned buffers must come from block 16 over global_num_experts"
-        sorted_p, experts_ptr, npost_p = ptr(a_sorted), ptr(a_experts), ptr(a_npost)
-    if a1_quant is None:
-        check(
-            lib.chitu_hip_act_quant_fp8(
-                ptr(hidden_states), float_dtype_code(hidden_states.dtype), i64(num_tokens), i64(K), i32(128),
-                i32(1), f32(1e-10), P("a1q"), P("a1s"), st,
-            ),
-            "moe quant1",
-        )
-        a1q_p, a1s_p = P("a1q"), P("a1s")
-    else:
-        aq, as_ = a1_quant
-        assert aq.is_contiguous() and as_.is_contiguous() and aq.numel() == num_tokens * K
-        assert as_.dtype == torch.float32 and as_.numel() == num_tokens * KB
-        a1q_p, a1s_p = ptr(aq), ptr(as_)
-    if tiled:
+    p = _MoePlan(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, aligned, reduce_topk)
+    if p.num_tokens == 0:
+        return p.out
+    num_tokens, K, N, I, Nout, topk, numel = p.num_tokens, p.K, p.N, p.I, p.Nout, p.topk, p.numel
+    topk_weights, block_m, max_mblocks, P, lib, st = p.topk_weights, p.block_m, p.max_mblocks, p.P, p.lib, p.st
+    sorted_p, experts_p, npost_p = p.align(
+        [("a1q", num_tokens * K), ("a1s", num_tokens * (K // 128) * 4), ("c1", numel * N * 2),
+         ("a2q", numel * I), ("a2s", numel * (I // 128) * 4), ("c3", numel * Nout * 2)], expert_map)
+    a1q_p, a1s_p = _quant1_fp8(p, hidden_states, a1_quant)
+    if p.tiled:
         # prefill: GEMM1 + SiLU-and-mul tiled, per-token-group quant of h, GEMM2 tiled (csrc/moe_tiled.hip)
-        assert nblk <= 65535
         check(
             lib.chitu_hip_moe_gemm1_silu_fp8_tiled(
-                a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_ptr, npost_p, P("c1"),
+                a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
                 i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), i32(block_m), st,
             ),
             "moe gemm1 (tiled, silu fused)",
@@ -398,7 +422,7 @@ def fused_experts_impl(
         )
         check(
             lib.chitu_hip_moe_gemm2_fp8_tiled(
-                P("a2q"), P("a2s"), ptr(w2), ptr(w2_scale), sorted_p, experts_ptr, npost_p,
+                P("a2q"), P("a2s"), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
                 ptr(topk_weights), float_dtype_code(topk_weights.dtype), i32(1), P("c3"), i64(numel), i64(Nout),
                 i64(I), i64(max_mblocks), i32(block_m), st,
             ),
@@ -411,14 +435,14 @@ def fused_experts_impl(
         # 512-wide expert hides and a 1408-wide one does not (profiles/r03_v2lite_wide_experts.txt).
         check(
             lib.chitu_hip_moe_gemm1_silu_fp8(
-                a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_ptr, npost_p, P("c1"),
+                a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
                 i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), st,
             ),
             "moe gemm1 (silu fused)",
         )
         check(
             lib.chitu_hip_moe_gemm2_quant_fp8(
-                P("c1"), ptr(w2), ptr(w2_scale), sorted_p, experts_ptr, npost_p, ptr(topk_weights),
+                P("c1"), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p, ptr(topk_weights),
                 float_dtype_code(topk_weights.dtype), i32(1), P("c3"), i64(numel), i64(Nout), i64(I),
                 i64(max_mblocks), f32(1e-10), st,
             ),
@@ -430,7 +454,7 @@ def fused_experts_impl(
         # its 8-wave workgroups halve the resident waves per CU -- and removed in round 5.)
         check(
             lib.chitu_hip_moe_gemm1_fp8(
-                a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_ptr, npost_p, P("c1"),
+                a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
                 i64(numel), i32(topk), i64(N), i64(K), i64(max_mblocks), st,
             ),
             "moe gemm1",
@@ -441,17 +465,32 @@ def fused_experts_impl(
         )
         check(
             lib.chitu_hip_moe_gemm2_fp8(
-                P("a2q"), P("a2s"), ptr(w2), ptr(w2_scale), sorted_p, experts_ptr, npost_p,
+                P("a2q"), P("a2s"), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
                 ptr(topk_weights), float_dtype_code(topk_weights.dtype), i32(1), P("c3"), i64(numel), i64(Nout),
                 i64(I), i64(max_mblocks), st,
             ),
             "moe gemm2",
         )
-    if not reduce_topk:
-        c3_off = off["c3"] - base
-        return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
-    check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
-    return out
+    return p.finish()
+
+
+def _quant1_fp8(p, hidden_states, a1_quant):
+    """(codes, scales) pointers of the tokens' per-128-group e4m3 form, for the fp8 and the MXFP4 experts: one quantiser
+    launch into the plan's "a1q" / "a1s", or the producer's a1_quant=(q, s) after its checks."""
+    if a1_quant is None:
+        check(
+            p.lib.chitu_hip_act_quant_fp8(
+                ptr(hidden_states), float_dtype_code(hidden_states.dtype), i64(p.num_tokens), i64(p.K), i32(128),
+                i32(1), f32(1e-10), p.P("a1q"), p.P("a1s"), p.st,
+            ),
+            "moe quant1",
+        )
+        return p.P("a1q"), p.P("a1s")
+    aq, as_ = a1_quant
+    require_cuda(aq, as_)
+    assert aq.is_contiguous() and as_.is_contiguous() and aq.element_size() == 1 and aq.numel() == p.num_tokens * p.K
+    assert as_.dtype == torch.float32 and as_.numel() == p.num_tokens * (p.K // 128)
+    return ptr(aq), ptr(as_)
 
 
 def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, expert_map,
@@ -475,7 +514,7 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
     assert w1_scale is not None and w2_scale is not None, "MXFP4 experts need their E8M0 scales"
     for t in (w1, w2, w1_scale, w2_scale):
         assert t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 3, "MXFP4 weights and scales are contiguous uint8 [E, rows, .]"
-    num_tokens, K = hidden_states.shape
+    K = hidden_states.shape[1]
     E, N, _ = w1.shape
     I = N // 2
     Nout = w2.shape[1]
@@ -483,63 +522,20 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
     assert tuple(w1.shape) == (E, N, K // 2) and tuple(w1_scale.shape) == (E, N, K // 32), "w1 [E, 2I, K/2], w1_scale [E, 2I, K/32]"
     assert tuple(w2.shape) == (E, Nout, I // 2) and tuple(w2_scale.shape) == (E, Nout, I // 32), "w2 [E, Nout, I/2], w2_scale [E, Nout, I/32]"
     require_cuda(hidden_states, w1, w2, topk_weights, topk_ids, w1_scale, w2_scale)
-    if global_num_experts == -1:
-        global_num_experts = E
-    topk = topk_ids.shape[1]
-    dev = hidden_states.device
-    out = hidden_states if inplace else torch.empty_like(hidden_states)
-    if num_tokens == 0:
-        return out
-    assert Nout == K or not reduce_topk, "the summed output has the hidden size"
-    numel = num_tokens * topk
-    topk_ids = topk_ids.contiguous()
-    topk_weights = topk_weights.contiguous()
-    tiled = _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, min_tokens=_MOE_MXFP4_TILED_MIN_TOKENS)
-    block_m = _MOE_TILED_BLOCK_M if tiled else _MOE_BLOCK_M
-    cap = numel + global_num_experts * (block_m - 1)
-    nblk = ceil_div(cap, block_m)
-    KB = K // 128
-    rnd = lambda n: (n + 255) // 256 * 256
-    sizes = [("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
-             ("a1q", num_tokens * K), ("a1s", num_tokens * KB * 4), ("c1", numel * N * 2),
-             ("a2q", numel * I), ("a2s", numel * (I // 128) * 4), ("c3", numel * Nout * 2)]
-    ws = workspace.get(sum(rnd(n) for _, n in sizes), dev, "moe")
-    base, off, cur = ws.data_ptr(), {}, 0
-    for name, n in sizes:
-        off[name] = base + cur
-        cur += rnd(n)
-    import ctypes as _ct
 
-    P = lambda name: _ct.c_void_p(off[name])
-    lib, st = _lib.lib(), stream_ptr()
-    max_mblocks = min(nblk, numel)
-    if aligned is None:
-        emap = _expert_map_i32(expert_map, global_num_experts, dev)
-        check(lib.chitu_hip_moe_align_block_size_mapped(ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel),
-                                                        i32(global_num_experts), i32(block_m), P("sorted"), i64(cap),
-                                                        P("experts"), i64(nblk), P("npost"), P("cumsum"), i32(1), ptr(emap), st),
-              "moe_align_block_size")
-        sorted_p, experts_p, npost_p = P("sorted"), P("experts"), P("npost")
-    else:
-        a_sorted, a_experts, a_npost = aligned
-        require_cuda(a_sorted, a_experts, a_npost)
-        assert a_sorted.dtype == torch.int32 and a_experts.dtype == torch.int32 and a_npost.dtype == torch.int32
-        assert a_sorted.numel() == cap and a_experts.numel() == nblk, "aligned buffers must come from block 16 over global_num_experts"
-        sorted_p, experts_p, npost_p = ptr(a_sorted), ptr(a_experts), ptr(a_npost)
-    if a1_quant is None:
-        check(lib.chitu_hip_act_quant_fp8(ptr(hidden_states), float_dtype_code(hidden_states.dtype), i64(num_tokens), i64(K),
-                                          i32(128), i32(1), f32(1e-10), P("a1q"), P("a1s"), st), "moe quant1")
-        a1q_p, a1s_p = P("a1q"), P("a1s")
-    else:
-        aq, as_ = a1_quant
-        require_cuda(aq, as_)
-        assert aq.is_contiguous() and as_.is_contiguous() and aq.element_size() == 1 and aq.numel() == num_tokens * K
-        assert as_.dtype == torch.float32 and as_.numel() == num_tokens * KB
-        a1q_p, a1s_p = ptr(aq), ptr(as_)
+    p = _MoePlan(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, aligned, reduce_topk,
+                 min_tokens=_MOE_MXFP4_TILED_MIN_TOKENS)
+    if p.num_tokens == 0:
+        return p.out
+    num_tokens, topk, numel = p.num_tokens, p.topk, p.numel
+    topk_weights, block_m, max_mblocks, P, lib, st = p.topk_weights, p.block_m, p.max_mblocks, p.P, p.lib, p.st
+    sorted_p, experts_p, npost_p = p.align(
+        [("a1q", num_tokens * K), ("a1s", num_tokens * (K // 128) * 4), ("c1", numel * N * 2),
+         ("a2q", numel * I), ("a2s", numel * (I // 128) * 4), ("c3", numel * Nout * 2)], expert_map)
+    a1q_p, a1s_p = _quant1_fp8(p, hidden_states, a1_quant)
     wdt = float_dtype_code(topk_weights.dtype)
-    if tiled:
+    if p.tiled:
         # prefill: GEMM1 + SiLU-and-mul tiled, per-token-group quant of h, GEMM2 tiled (csrc/moe_mxfp4_tiled.hip)
-        assert nblk <= 65535
         check(lib.chitu_hip_moe_gemm1_silu_mxfp4_tiled(a1q_p, a1s_p, ptr(w1), ptr(w1_scale), sorted_p, experts_p, npost_p, P("c1"),
                                                        i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), i32(block_m), st),
               "moe mxfp4 gemm1 (tiled, silu fused)")
@@ -564,11 +560,7 @@ def _fused_experts_mxfp4(hidden_states, w1, w2, topk_weights, topk_ids, inplace,
         check(lib.chitu_hip_moe_gemm_mxfp4(P("a2q"), P("a2s"), i32(1), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
                                            ptr(topk_weights), i32(wdt), i32(1), P("c3"), i64(numel), i64(Nout), i64(I),
                                            i64(max_mblocks), st), "moe mxfp4 gemm2")
-    if not reduce_topk:
-        c3_off = off["c3"] - base
-        return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
-    check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
-    return out
+    return p.finish()
 
 
 def _fused_experts_int8(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, expert_map,
@@ -577,55 +569,25 @@ def _fused_experts_int8(hidden_states, w1, w2, topk_weights, topk_ids, inplace, 
     int8 weights.  w1 [E, 2I, K] int8, w1_scale [E, 2I]; w2 [E, N, I] int8, w2_scale [E, N].
     align(16) -> quant_act -> grouped GEMM1 (+ silu*mul) -> quant_act -> grouped GEMM2 (x routed weight) -> sum:
     the per-expert W8A8Linear arithmetic of the reference's expert loop (model_hf_mixtral.py:76-94,
-    quantize/w8a8.py:97-132), grouped."""
+    quantize/w8a8.py:97-132), grouped.  There is no tiled form."""
     assert hidden_states.dtype == torch.bfloat16 and w1.dtype == torch.int8 and w2.dtype == torch.int8
     assert w1_scale is not None and w2_scale is not None and w1_scale.dtype == torch.float32 and w2_scale.dtype == torch.float32
     require_cuda(hidden_states, w1, w2, topk_weights, topk_ids, w1_scale, w2_scale)
-    num_tokens, K = hidden_states.shape
+    K = hidden_states.shape[1]
     E, N, _ = w1.shape
     I = N // 2
     Nout = w2.shape[1]
     assert w2.shape[0] == E and w2.shape[2] == I and tuple(w1_scale.shape) == (E, N) and tuple(w2_scale.shape) == (E, Nout)
     assert w1_scale.is_contiguous() and w2_scale.is_contiguous() and K % 128 == 0 and I % 128 == 0
-    if global_num_experts == -1:
-        global_num_experts = E
-    topk = topk_ids.shape[1]
-    dev = hidden_states.device
-    out = hidden_states if inplace else torch.empty_like(hidden_states)
-    if num_tokens == 0:
-        return out
-    numel = num_tokens * topk
-    topk_ids = topk_ids.contiguous()
-    topk_weights = topk_weights.contiguous()
-    cap = numel + global_num_experts * (_MOE_BLOCK_M - 1)
-    nblk = ceil_div(cap, _MOE_BLOCK_M)
-    rnd = lambda n: (n + 255) // 256 * 256
-    sizes = [("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
-             ("xq", num_tokens * K), ("xs", num_tokens * 4), ("a", numel * I * 2), ("aq", numel * I), ("as", numel * 4),
-             ("c3", numel * Nout * 2)]
-    ws = workspace.get(sum(rnd(n) for _, n in sizes), dev, "moe")
-    base, off, cur = ws.data_ptr(), {}, 0
-    for name, n in sizes:
-        off[name] = base + cur
-        cur += rnd(n)
-    import ctypes as _ct
 
-    P = lambda name: _ct.c_void_p(off[name])
-    lib, st = _lib.lib(), stream_ptr()
-    max_mblocks = min(nblk, numel)
-    if aligned is None:
-        emap = _expert_map_i32(expert_map, global_num_experts, hidden_states.device)
-        check(lib.chitu_hip_moe_align_block_size_mapped(ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel),
-                                                        i32(global_num_experts), i32(_MOE_BLOCK_M), P("sorted"), i64(cap),
-                                                        P("experts"), i64(nblk), P("npost"), P("cumsum"), i32(1), ptr(emap), st),
-              "moe_align_block_size")
-        sorted_p, experts_p, npost_p = P("sorted"), P("experts"), P("npost")
-    else:  # the router's launch already sorted the ids (ops.gate_deepseek_v3(align=...)): one launch less per layer
-        a_sorted, a_experts, a_npost = aligned
-        require_cuda(a_sorted, a_experts, a_npost)
-        assert a_sorted.dtype == torch.int32 and a_experts.dtype == torch.int32 and a_npost.dtype == torch.int32
-        assert a_sorted.numel() == cap and a_experts.numel() == nblk, "aligned buffers must come from block 16 over global_num_experts"
-        sorted_p, experts_p, npost_p = ptr(a_sorted), ptr(a_experts), ptr(a_npost)
+    p = _MoePlan(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, aligned, reduce_topk, tiles=False)
+    if p.num_tokens == 0:
+        return p.out
+    num_tokens, topk, numel = p.num_tokens, p.topk, p.numel
+    topk_weights, max_mblocks, P, lib, st = p.topk_weights, p.max_mblocks, p.P, p.lib, p.st
+    sorted_p, experts_p, npost_p = p.align(
+        [("xq", num_tokens * K), ("xs", num_tokens * 4), ("a", numel * I * 2), ("aq", numel * I), ("as", numel * 4),
+         ("c3", numel * Nout * 2)], expert_map)
     if a1_quant is None:
         check(lib.chitu_hip_quant_act_int8(ptr(hidden_states), float_dtype_code(hidden_states.dtype), i64(num_tokens), i64(K),
                                            P("xq"), P("xs"), st), "moe int8 quant1")
@@ -642,11 +604,7 @@ def _fused_experts_int8(hidden_states, w1, w2, topk_weights, topk_ids, inplace, 
     check(lib.chitu_hip_moe_i8_gemm2(P("aq"), P("as"), ptr(w2), ptr(w2_scale), sorted_p, experts_p, npost_p,
                                      ptr(topk_weights), float_dtype_code(topk_weights.dtype), i32(1), P("c3"), i64(numel),
                                      i64(Nout), i64(I), i64(max_mblocks), st), "moe int8 gemm2")
-    if not reduce_topk:
-        c3_off = off["c3"] - base
-        return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
-    check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
-    return out
+    return p.finish()
 
 
 def _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, expert_map,
@@ -668,78 +626,35 @@ def _fused_experts_bf16_act(hidden_states, w1, w2, topk_weights, topk_ids, inpla
     else:
         assert w1.dtype == torch.bfloat16 and w2.dtype == torch.bfloat16, "bf16 expert weights"
     require_cuda(hidden_states, w1, w2, topk_weights, topk_ids, w1_scale, w2_scale)
-    num_tokens, K = hidden_states.shape
-    E, N, _ = w1.shape
-    I = N // 2
-    assert w2.shape[0] == E and w2.shape[2] == I, "w2 must be [E, hidden_out, N/2]"
-    Nout = w2.shape[1]
+    K, I = hidden_states.shape[1], w1.shape[1] // 2
+    assert w2.shape[0] == w1.shape[0] and w2.shape[2] == I, "w2 must be [E, hidden_out, N/2]"
     assert K % 128 == 0 and I % 128 == 0, "K and the expert width must be multiples of 128"
-    if global_num_experts == -1:
-        global_num_experts = E
-    topk = topk_ids.shape[1]
-    dev = hidden_states.device
-    out = hidden_states if inplace else torch.empty_like(hidden_states)
-    if num_tokens == 0:
-        return out
-    numel = num_tokens * topk
-    topk_ids = topk_ids.contiguous()
-    topk_weights = topk_weights.contiguous()
-    floor = _MOE_BF16_TILED_MIN_TOKENS if tiled_min_tokens is None else int(tiled_min_tokens)
-    tiled = not soft and _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, min_tokens=floor)
-    block_m = _MOE_TILED_BLOCK_M if tiled else _MOE_BLOCK_M
-    cap = numel + global_num_experts * (block_m - 1)
-    nblk = ceil_div(cap, block_m)
-    rnd = lambda n: (n + 255) // 256 * 256
-    sizes = [("sorted", cap * 4), ("experts", nblk * 4), ("npost", 4), ("cumsum", (global_num_experts + 1) * 4),
-             ("h", numel * I * 2), ("c3", numel * Nout * 2)]
-    ws = workspace.get(sum(rnd(n) for _, n in sizes), dev, "moe")
-    base, off, cur = ws.data_ptr(), {}, 0
-    for name, n in sizes:
-        off[name] = base + cur
-        cur += rnd(n)
-    import ctypes as _ct
 
-    P = lambda name: _ct.c_void_p(off[name])
-    lib, st = _lib.lib(), stream_ptr()
-    max_mblocks = min(nblk, numel)
-    if aligned is None:
-        emap = _expert_map_i32(expert_map, global_num_experts, dev)
-        check(lib.chitu_hip_moe_align_block_size_mapped(ptr(topk_ids), int_dtype_code(topk_ids.dtype), i64(numel),
-                                                        i32(global_num_experts), i32(block_m), P("sorted"), i64(cap),
-                                                        P("experts"), i64(nblk), P("npost"), P("cumsum"), i32(1), ptr(emap), st),
-              "moe_align_block_size")
-        sorted_p, experts_ptr, npost_p = P("sorted"), P("experts"), P("npost")
-    else:
-        a_sorted, a_experts, a_npost = aligned
-        require_cuda(a_sorted, a_experts, a_npost)
-        assert a_sorted.numel() == cap and a_experts.numel() == nblk, "aligned buffers must come from block 16 over global_num_experts"
-        sorted_p, experts_ptr, npost_p = ptr(a_sorted), ptr(a_experts), ptr(a_npost)
+    floor = _MOE_BF16_TILED_MIN_TOKENS if tiled_min_tokens is None else int(tiled_min_tokens)
+    p = _MoePlan(hidden_states, w1, w2, topk_weights, topk_ids, inplace, global_num_experts, aligned, reduce_topk,
+                 tiles=not soft, min_tokens=floor)
+    if p.num_tokens == 0:
+        return p.out
+    Nout, topk, numel = p.Nout, p.topk, p.numel
+    topk_weights, block_m, max_mblocks, P, lib, st = p.topk_weights, p.block_m, p.max_mblocks, p.P, p.lib, p.st
+    sorted_p, experts_p, npost_p = p.align([("h", numel * I * 2), ("c3", numel * Nout * 2)], expert_map)
     kind = i32(1 if soft else 0)
-    if tiled:
+    if p.tiled:
         # prefill: GEMM1 + SiLU-and-mul tiled, GEMM2 tiled (csrc/moe_bf16_tiled.hip); h stays bf16, nothing is quantised
-        assert nblk <= 65535
-        check(lib.chitu_ext3_moe_gemm1_silu_bf16_tiled(ptr(hidden_states), ptr(w1), sorted_p, experts_ptr, npost_p, P("h"),
+        check(lib.chitu_ext3_moe_gemm1_silu_bf16_tiled(ptr(hidden_states), ptr(w1), sorted_p, experts_p, npost_p, P("h"),
                                                        i64(numel), i32(topk), i64(I), i64(K), i64(max_mblocks), i32(block_m), st),
               "moe bf16 gemm1 (tiled, silu fused)")
-        check(lib.chitu_ext3_moe_gemm2_bf16_tiled(P("h"), ptr(w2), sorted_p, experts_ptr, npost_p, ptr(topk_weights),
+        check(lib.chitu_ext3_moe_gemm2_bf16_tiled(P("h"), ptr(w2), sorted_p, experts_p, npost_p, ptr(topk_weights),
                                                   i32(float_dtype_code(topk_weights.dtype)), i32(1), P("c3"), i64(numel), i64(Nout),
                                                   i64(I), i64(max_mblocks), i32(block_m), st), "moe bf16 gemm2 (tiled)")
-        if not reduce_topk:
-            c3_off = off["c3"] - base
-            return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
-        check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
-        return out
-    check(lib.chitu_hip_moe_gemm_bf16(ptr(hidden_states), i32(topk), ptr(w1), ptr(w1_scale), kind, sorted_p, experts_ptr,
-                                      npost_p, ptr(None), i32(0), i32(0), i32(1), P("h"), i64(numel), i64(I), i64(K),
-                                      i64(max_mblocks), st), "moe gemm1 (bf16 activations, silu fused)")
-    check(lib.chitu_hip_moe_gemm_bf16(P("h"), i32(1), ptr(w2), ptr(w2_scale), kind, sorted_p, experts_ptr, npost_p,
-                                      ptr(topk_weights), float_dtype_code(topk_weights.dtype), i32(1), i32(0), P("c3"),
-                                      i64(numel), i64(Nout), i64(I), i64(max_mblocks), st), "moe gemm2 (bf16 activations)")
-    if not reduce_topk:
-        c3_off = off["c3"] - base
-        return ws[c3_off : c3_off + numel * Nout * 2].view(torch.bfloat16).view(num_tokens, topk, Nout)
-    check(lib.chitu_hip_moe_sum(P("c3"), ptr(out), i64(num_tokens), i32(topk), i64(Nout), st), "moe sum")
-    return out
+    else:
+        check(lib.chitu_hip_moe_gemm_bf16(ptr(hidden_states), i32(topk), ptr(w1), ptr(w1_scale), kind, sorted_p, experts_p,
+                                          npost_p, ptr(None), i32(0), i32(0), i32(1), P("h"), i64(numel), i64(I), i64(K),
+                                          i64(max_mblocks), st), "moe gemm1 (bf16 activations, silu fused)")
+        check(lib.chitu_hip_moe_gemm_bf16(P("h"), i32(1), ptr(w2), ptr(w2_scale), kind, sorted_p, experts_p, npost_p,
+                                          ptr(topk_weights), float_dtype_code(topk_weights.dtype), i32(1), i32(0), P("c3"),
+                                          i64(numel), i64(Nout), i64(I), i64(max_mblocks), st), "moe gemm2 (bf16 activations)")
+    return p.finish()
 
 
 def silu_and_mul_quant(x: torch.Tensor, mode: str = "act"):

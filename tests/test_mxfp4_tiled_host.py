@@ -77,18 +77,76 @@ def test_mxfp4_path_switches_over_at_its_own_token_count(monkeypatch):
     assert fused_moe._takes_tiled(2048, 2048 * 8, 32, 256, 7168, None, min_tokens=512) is False
 
 
-def test_both_paths_call_the_one_predicate():
-    """The fp8 path and the MXFP4 path decide through _takes_tiled and nothing else."""
-    import inspect
+def test_every_format_decides_through_the_one_predicate(monkeypatch):
+    """One fused_experts call asks _takes_tiled once, with the format's own token floor and nothing else of its own; the
+    formats without a tiled form never ask; and the answer alone sets the align block and the GEMM entries (fake library:
+    tests/moe_plan_exact.py).  All five modes in turn."""
+    for mode in ("fp8", "soft_fp8", "bf16", "int8", "mxfp4"):
+        with monkeypatch.context() as patch:
+            _decides_through_the_one_predicate(mode, patch)
+
+
+def _decides_through_the_one_predicate(mode, monkeypatch):
+    from chitu_amd import fused_moe
+    from tests import moe_plan_exact as mp
+
+    asked = []
+    force = [None]
+    real = fused_moe._takes_tiled
+
+    def predicate(*args, **kw):
+        asked.append((args, kw))
+        return real(*args, **kw) if force[0] is None else force[0]
+
+    monkeypatch.setattr(fused_moe, "_takes_tiled", predicate)
+    tiles = mode in ("fp8", "bf16", "mxfp4")
+    c = mp.case(mode, tokens=mp.PREFILL, block_m=64)
+    floor = {"fp8": None, "mxfp4": 512, "bf16": 0}  # what mp.substituted pins the module's defaults to
+    plans = {}
+    for force[0] in (None, True, False):
+        del asked[:]
+        plans[force[0]] = mp.record(fused_moe, c)
+        if not tiles:
+            assert asked == []
+            continue
+        (args, kw), = asked
+        assert args[:5] == (mp.PREFILL, mp.PREFILL * mp.TOPK, mp.E, 128, mp.K)
+        assert (list(args[5:]) + [kw.get("aligned")])[0] is None
+        assert (list(args[6:]) + [kw.get("min_tokens")])[0] == floor[mode]
+
+    def shape(plan):
+        entries = [e for e, _ in plan["calls"]]
+        align = plan["calls"][0][1]
+        return entries[0], align[4], [e for e in entries if e.endswith("_tiled")]
+
+    if not tiles:
+        assert plans[None] == plans[True] == plans[False] and shape(plans[None]) == ("chitu_hip_moe_align_block_size_mapped", ["i32", 16], [])
+        return
+    assert shape(plans[False]) == ("chitu_hip_moe_align_block_size_mapped", ["i32", 16], [])
+    entry, block, tiled = shape(plans[True])
+    assert block == ["i32", 64] and len(tiled) == 2 and tiled[0].startswith(("chitu_hip_moe_gemm1_silu_", "chitu_ext3_moe_gemm1_silu_"))
+    assert [e for e, _ in plans[True]["calls"] if "gemm" in e] == tiled  # no streaming GEMM beside them
+    assert plans[None] == plans[mode == "fp8"]  # at the defaults 200 tokens tile the fp8 experts only
+    # the per-call floor of the bf16 experts reaches the predicate as it is
+    if mode == "bf16":
+        del asked[:]
+        mp.record(fused_moe, mp.case(mode, tokens=mp.PREFILL, bf16_floor=131))
+        assert asked[0][1].get("min_tokens", (asked[0][0] + (None,) * 7)[6]) == 131
+
+
+def test_only_the_predicate_reads_the_tiled_thresholds():
+    import ast
 
     from chitu_amd import fused_moe
 
-    for fn, call in ((fused_moe.fused_experts_impl, "tiled = _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned)"),
-                     (fused_moe._fused_experts_mxfp4, "tiled = _takes_tiled(num_tokens, numel, global_num_experts, I, Nout, aligned, "
-                                                      "min_tokens=_MOE_MXFP4_TILED_MIN_TOKENS)")):
-        src = inspect.getsource(fn)
-        assert call in src, fn.__name__
-        assert "_MOE_TILED_MIN_TOKENS" not in src and "_MOE_TILED_MIN_PER_EXPERT" not in src, fn.__name__
+    tree = ast.parse(open(fused_moe.__file__).read())
+    readers = {}
+    for node in ast.walk(tree):
+        if isinstance(node, (ast.FunctionDef, ast.ClassDef)):
+            for sub in ast.walk(node):
+                if isinstance(sub, ast.Name) and sub.id in ("_MOE_TILED_MIN_TOKENS", "_MOE_TILED_MIN_PER_EXPERT"):
+                    readers.setdefault(sub.id, set()).add(node.name)
+    assert readers == {"_MOE_TILED_MIN_TOKENS": {"_takes_tiled"}, "_MOE_TILED_MIN_PER_EXPERT": {"_takes_tiled"}}
 
 
 # ---------------------------------------------------------------- header and ABI
