@@ -235,6 +235,13 @@ class PagedKVCacheManager:
         steady decode that is one step in `block_size`."""
         n = len(req_ids)
         changed = self._table_rows is None or self._table_rows != list(req_ids)
+        need = 0
+        for req_id in req_ids:  # every request's capacity and the free pages first: a refused step has taken no page
+            if self.seq_lens[req_id] + 1 > self.max_blocks_per_req * self.block_size:
+                raise Exception(f"request {req_id!r}: {self.seq_lens[req_id]} + 1 tokens do not fit its block table")
+            need += self.seq_lens[req_id] % self.block_size == 0
+        if need > len(self.free_blocks):
+            raise Exception(f"{need} more pages for {n} tokens do not fit the {len(self.free_blocks)} free pages")
         for req_id in req_ids:
             if self.seq_lens[req_id] % self.block_size == 0:
                 self.block_table[req_id].append(self.get_free_block())
@@ -282,9 +289,13 @@ class PagedKVCacheManager:
         assert 1 <= T <= MAX_DECODE_Q
         n = len(req_ids)
         assert n * MAX_DECODE_Q <= self._multi_buffers().numel()
-        for req_id in req_ids:  # every request's capacity first: a refused step has taken no page
+        need = 0
+        for req_id in req_ids:  # every request's capacity and the free pages first: a refused step has taken no page
             if self.seq_lens[req_id] + T > self.max_blocks_per_req * self.block_size:
                 raise Exception(f"request {req_id!r}: {self.seq_lens[req_id]} + {T} tokens do not fit its block table")
+            need += max(0, -(-(self.seq_lens[req_id] + T) // self.block_size) - len(self.block_table[req_id]))
+        if need > len(self.free_blocks):
+            raise Exception(f"{need} more pages for {n} x {T} tokens do not fit the {len(self.free_blocks)} free pages")
         for req_id in req_ids:
             while len(self.block_table[req_id]) * self.block_size < self.seq_lens[req_id] + T:
                 self.block_table[req_id].append(self.get_free_block())
