@@ -14,6 +14,7 @@ from oracle import mla as omla
 from tests import attn_exact as ax
 from tests import test_gqa_kv_fp8_host as g8
 from tests import test_mla_kv_fp8_host as m8
+from tests.big_cache import first_page_beyond_4gib, need_free, place_and_append  # the helpers of the beyond-4-GiB tests
 from tests.util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -259,48 +260,6 @@ def test_mla_prefill_every_query_row_is_its_own_length_sweep(H, mode, monkeypatc
 
 
 # ---------------------------------------------------------------- byte offsets beyond 4 GiB
-def first_page_beyond_4gib(page_bytes):
-    return 2 ** 32 // page_bytes + 1
-
-
-def need_free(nbytes):
-    free, _ = torch.cuda.mem_get_info()
-    if free < 3 * nbytes:
-        pytest.skip(f"{nbytes / 2**30:.1f} GiB cache: needs {3 * nbytes / 2**30:.0f} GiB free, {free / 2**30:.0f} GiB are")
-
-
-def place_and_append(caches, rows, fills, tables, lens, quant, append):
-    """Write every sequence's rows but its last into its pages (the pages' other rows and page 0 hold fills[c] everywhere: what a
-    wrongly admitted key would show), append the last row through the project's append op, and assert that exactly the addressed
-    rows of the named pages changed, page 0 not at all.  caches / rows / fills: one entry per cache (K and V, or the one MLA
-    cache); rows[c][s]: [n_s, ...] bf16 logical rows of sequence s."""
-    page = caches[0].shape[1]
-    ids = sorted({int(p) for t in tables for p in t})
-    want = []
-    for cache, seq_rows, fill in zip(caches, rows, fills):
-        sentinel = quant(torch.full((page,) + tuple(seq_rows[0].shape[1:]), fill, dtype=torch.bfloat16))
-        cache[0] = sentinel.cuda()
-        for i in ids:
-            cache[i] = sentinel.cuda()
-        for r, t, n in zip(seq_rows, tables, lens):
-            for p in range((n + page - 1) // page):
-                stop = min(n - 1, (p + 1) * page)
-                if stop > p * page:
-                    cache[int(t[p]), : stop - p * page] = quant(r[p * page : stop]).cuda()
-        w = cache[ids].cpu()
-        for r, t, n in zip(seq_rows, tables, lens):
-            w[ids.index(int(t[(n - 1) // page])), (n - 1) % page] = quant(r[n - 1 : n])[0]
-        want.append((w, sentinel))
-    width = max(len(t) for t in tables)
-    table = torch.tensor([list(t) + [t[-1]] * (width - len(t)) for t in tables], dtype=torch.int32).cuda()
-    old = torch.tensor([n - 1 for n in lens], dtype=torch.int32).cuda()
-    append(table, [torch.stack([r[n - 1] for r, n in zip(seq_rows, lens)]).cuda() for seq_rows in rows], old)
-    for cache, (w, sentinel) in zip(caches, want):
-        assert torch.equal(cache[ids].cpu(), w), "the append changed another row of the named pages, or not the addressed one"
-        assert torch.equal(cache[0].cpu(), sentinel), "the append wrote into page 0"
-    return table
-
-
 @pytest.mark.parametrize("fp8", [False, True], ids=["bf16", "fp8"])
 def test_gqa_caches_beyond_4gib(fp8):
     """K / V caches whose every named page lies more than 2^32 bytes into the allocation (page 256, 8 KV heads: page ids above 8192;
