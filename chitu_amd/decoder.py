@@ -218,14 +218,19 @@ class DecoderBase(torch.nn.Module):
     # ------------------------------------------------------------------ generation
     @torch.inference_mode()
     def generate(self, prompts, max_new_tokens, req_ids=None, use_graph=True, temperatures=None, top_ks=None,
-                 top_ps=None, frequency_penalties=None, generator=None, prefill_chunk_size=None):
+                 top_ps=None, frequency_penalties=None, generator=None, prefill_chunk_size=None, logprobs=None):
         """Prefill (prefill_chunk_size: in chunks, prefill's chunk_size), then max_new_tokens - 1 decode steps; returns
         [n_req, max_new_tokens] int64 and frees the requests' pages.  Token selection is executor.py:82-112 on the device
         (chitu_amd.sampling): greedy unless some top_k > 1 (then per-request temperature / top-k / top-p sampling, uniforms from
-        `generator`), with an optional per-request frequency penalty; tokens never visit the host."""
+        `generator`), with an optional per-request frequency penalty; tokens never visit the host.
+
+        logprobs = N (0 .. 20): returns (tokens, lp) instead, lp a sampling.LogProbs on the HOST -- every emitted token's
+        log-probability [n_req, max_new_tokens] and the N most likely tokens with theirs [n_req, max_new_tokens, N], under
+        softmax(logits) as the model gave them (before temperature, top-k / top-p and the penalty).  One more launch per step
+        (DeviceSampler), nothing visits the host before the end; the first token's entries come from the prefill logits."""
         req_ids = [f"gen{i}" for i in range(len(prompts))] if req_ids is None else list(req_ids)
         pick = sampling.DeviceSampler(len(prompts), max_new_tokens, self.device, temperatures, top_ks, top_ps,
-                                      frequency_penalties, generator)
+                                      frequency_penalties, generator, logprobs)
         tok = pick(self.prefill(prompts, req_ids) if prefill_chunk_size is None else
                    self.prefill(prompts, req_ids, chunk_size=prefill_chunk_size))
         out = [tok]
@@ -242,6 +247,8 @@ class DecoderBase(torch.nn.Module):
             # the tokens are about to leave the engine: make sure no collective behind them gave up on a peer
             torch.cuda.current_stream().synchronize()
             tp.check_comm()
+        if pick.logprobs is not None:
+            return tokens_out, sampling.LogProbs(*(t.cpu() for t in pick.logprobs))
         return tokens_out
 
     @torch.inference_mode()

@@ -20,13 +20,16 @@ draft-and-verify loops of the decoders' generate_speculative / generate_speculat
 device with ONE `chitu_hip_speculative_verify` call per round (`speculative_verify`; rule and proof in DESIGN 3.9).  `ModelDrafter`
 drafts with a second, smaller decoder of this package on the device; where it samples its drafts the round is judged by
 `chitu_hip_speculative_verify_sampled` (`speculative_verify_sampled`: accept with min(1, p / q), replace from max(p - q, 0)).
+Log-probabilities of the emitted tokens and the N <= 20 most likely alternatives: `logprobs`, ONE `chitu_ext8_logprobs` launch
+(csrc/logprobs.hip); `DeviceSampler(..., logprobs=N)` keeps them on the device for generate().
 """
 
-from typing import List, Optional, Sequence, Tuple
+import ctypes
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, workspace
 from ._lib import check, float_dtype_code, i32, i64, ptr, require_cuda, stream_ptr
 
 __all__ = [
@@ -35,6 +38,8 @@ __all__ = [
     "top_k_top_p_sampling_from_logits",
     "top_k_top_p_min_p_sampling_from_probs_torch",
     "sample_tokens",
+    "logprobs",
+    "LogProbs",
     "DeviceSampler",
     "NgramDrafter",
     "ModelDrafter",
@@ -113,6 +118,71 @@ def argmax(logits: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Te
     return _launch(logits, None, None, None, None, 0, out, False)
 
 
+class LogProbs(NamedTuple):
+    """What generate(..., logprobs=N) reports beside the tokens, per request and emitted token: the token's log-probability
+    [n_req, max_new_tokens] f32, the N most likely tokens [.., N] int32 and their log-probabilities [.., N] f32 (descending,
+    equal values by the lower id first; id -1 / -inf at positions beyond the vocabulary)."""
+    token_logprobs: torch.Tensor
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+
+
+MAX_TOP_LOGPROBS = 20
+
+_logprobs_tickets = {}  # (device index, workspace namespace) -> the ticket buffer that has been zeroed
+
+
+def _logprobs_workspace(rows, vocab, top_n, device):
+    """(tickets, partials) of chitu_ext8_logprobs from the persistent workspace.  The kernel needs its tickets zero before the
+    first launch and leaves them zero: a ticket buffer is cleared once, when workspace.get created (or grew) it -- never under
+    graph capture, which workspace.get refuses."""
+    nt, npart = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(_lib.lib().chitu_ext8_logprobs_workspace_bytes(i64(rows), i32(vocab), i32(top_n), ctypes.byref(nt), ctypes.byref(npart)),
+          "logprobs_workspace_bytes")
+    tickets = workspace.get(nt.value, device, "logprobs_tickets")
+    partials = workspace.get(npart.value, device, "logprobs_partials")
+    key = (torch.device(device).index or 0, workspace._namespace)
+    if _logprobs_tickets.get(key) is not tickets:
+        tickets.zero_()
+        _logprobs_tickets[key] = tickets
+    return tickets, partials
+
+
+def logprobs(logits: torch.Tensor, tokens: Optional[torch.Tensor] = None, top_n: int = 0, out=None):
+    """Log-softmax statistics of logits [rows, vocab] (fp32 or bf16, any row stride, read only) in ONE chitu_ext8_logprobs
+    launch, without a sort and without a normalised copy of the row: (token_logprobs f32 [rows] -- log softmax(logits)[r, tokens[r]],
+    NaN for an id outside the vocabulary; None without `tokens` --, top_ids int32 [rows, top_n], top_logprobs f32 [rows, top_n]):
+    the top_n <= 20 most likely tokens in descending order, equal logits by the lower id first (the sampler's tie rule), id -1 and
+    -inf at positions >= vocab.  out: (token_logprobs | None, top_ids, top_logprobs) to write into instead -- rows of larger
+    tensors will do (any row stride, unit stride along top_n).  hipGraph-capturable after one eager call of the same size."""
+    require_cuda(logits, tokens)
+    top_n = int(top_n)
+    if not 0 <= top_n <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs: top_n={top_n}; 0 .. {MAX_TOP_LOGPROBS} alternatives are reported")
+    x2, rows, vocab = _rows(logits)
+    dev = logits.device
+    if out is None:
+        tok_lp = None if tokens is None else torch.empty(rows, dtype=torch.float32, device=dev)
+        top_ids = torch.empty(rows, top_n, dtype=torch.int32, device=dev)
+        top_lp = torch.empty(rows, top_n, dtype=torch.float32, device=dev)
+    else:
+        tok_lp, top_ids, top_lp = out
+    if tokens is not None:
+        assert tokens.dtype == torch.int64 and tokens.numel() == rows and tokens.is_contiguous()
+        assert tok_lp is not None and tok_lp.dtype == torch.float32 and tuple(tok_lp.shape) == (rows,)
+    else:
+        assert tok_lp is None
+    assert top_ids.dtype == torch.int32 and top_lp.dtype == torch.float32
+    assert tuple(top_ids.shape) == tuple(top_lp.shape) == (rows, top_n) and top_ids.stride() == top_lp.stride()
+    assert top_n == 0 or (top_ids.stride(1) == 1 and (rows == 1 or top_ids.stride(0) >= top_n))
+    tickets, partials = _logprobs_workspace(rows, vocab, top_n, dev)
+    check(_lib.lib().chitu_ext8_logprobs(
+        ptr(x2), float_dtype_code(x2.dtype), i64(x2.stride(0) if rows > 1 else vocab), i64(rows), i32(vocab), ptr(tokens), ptr(tok_lp),
+        i64(tok_lp.stride(0) if tok_lp is not None else 0), i32(top_n), ptr(top_ids), ptr(top_lp), i64(max(top_ids.stride(0), top_n)),
+        ptr(tickets), i64(tickets.numel()), ptr(partials), i64(partials.numel()), stream_ptr()), "logprobs")
+    return tok_lp, top_ids, top_lp
+
+
 def _per_row(v, rows, dtype, device):
     if isinstance(v, torch.Tensor):
         t = v.to(device=device, dtype=dtype).contiguous().view(-1)
@@ -176,10 +246,15 @@ class DeviceSampler:
     penalty launch, one sampling launch, and the bookkeeping copies.
 
     Greedy iff every top_k <= 1 (`is_all_greedy`, task.py:457) -- also the default when no sampling
-    parameter is given.  `generator`: a CUDA torch.Generator for the uniforms (reproducible runs)."""
+    parameter is given.  `generator`: a CUDA torch.Generator for the uniforms (reproducible runs).
+
+    logprobs = N (0 .. 20): every call also runs ONE chitu_ext8_logprobs launch on the model's logits with the tokens it just
+    chose, into self.logprobs (a LogProbs of device buffers [n_req, max_new_tokens(, N)], column t = call t): log softmax(logits)
+    as the model gave them -- before temperature, top-k / top-p and the frequency penalty, which then works (with the draw) on
+    a copy.  None: no launch and no allocation beyond the above."""
 
     def __init__(self, n_req: int, max_new_tokens: int, device, temperatures=None, top_ks=None, top_ps=None,
-                 frequency_penalties=None, generator=None):
+                 frequency_penalties=None, generator=None, logprobs=None):
         self.n_req, self.device, self.generator = n_req, torch.device(device), generator
         ks = [1] * n_req if top_ks is None else [int(k) for k in (top_ks.tolist() if isinstance(top_ks, torch.Tensor) else top_ks)]
         assert len(ks) == n_req
@@ -196,11 +271,25 @@ class DeviceSampler:
             self.history = torch.zeros(n_req, max(max_new_tokens, 1), dtype=torch.int32, device=self.device)
             self.row_ids = torch.arange(n_req + 1, dtype=torch.int32, device=self.device)
         self.n_generated = 0
+        self.logprobs = None
+        if logprobs is not None:
+            n_top = int(logprobs)
+            if not 0 <= n_top <= MAX_TOP_LOGPROBS:
+                raise ValueError(f"DeviceSampler: logprobs={logprobs}; 0 .. {MAX_TOP_LOGPROBS} alternatives are reported")
+            steps = max(max_new_tokens, 1)
+            self.logprobs = LogProbs(torch.empty(n_req, steps, dtype=torch.float32, device=self.device),
+                                     torch.empty(n_req, steps, n_top, dtype=torch.int32, device=self.device),
+                                     torch.empty(n_req, steps, n_top, dtype=torch.float32, device=self.device))
 
     def __call__(self, logits: torch.Tensor) -> torch.Tensor:
         lg, rows, _ = _rows(logits)
         assert rows == self.n_req
         t = self.n_generated
+        model_logits = lg
+        if self.logprobs is not None:
+            assert t < self.logprobs.token_logprobs.shape[1], "DeviceSampler: more calls than max_new_tokens (the logprobs buffers are full)"
+            if self.penalise and t > 0:
+                lg = lg.clone()  # the penalty works in place: it and the draw take a copy, the logprobs launch the model's logits
         if self.penalise:
             assert t <= self.history.shape[1], "DeviceSampler: more calls than max_new_tokens (the penalty history is full)"
         if self.penalise and t > 0:
@@ -213,6 +302,9 @@ class DeviceSampler:
             tok = top_k_top_p_sampling_from_logits(lg, self.temperatures, self.top_ks, self.top_ps, generator=self.generator)
         if self.penalise and t < self.history.shape[1]:
             self.history[:, t] = tok.to(torch.int32)
+        if self.logprobs is not None:
+            lp = self.logprobs
+            logprobs(model_logits, tok, lp.top_ids.shape[2], out=(lp.token_logprobs[:, t], lp.top_ids[:, t], lp.top_logprobs[:, t]))
         self.n_generated = t + 1
         return tok
 
