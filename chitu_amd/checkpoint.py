@@ -578,6 +578,8 @@ def load_checkpoint_hf_llama(model, path: str, rank: int = 0, world: int = 1, sk
     st = to_mixtral_module_names(st, args.num_local_experts) if mixtral else to_llama_module_names(st, qkv_bias=getattr(args, "qkv_bias", False))
     if getattr(args, "quant", None) == "w8a16":
         st = llama_to_w8a16(st)
+    elif getattr(args, "quant", None) == "w4a16g128":
+        st = llama_to_w4a16(st)
     load_deepseek_v3(model, st)  # the generic strict, shape- and dtype-checked in-place copy
 
 
@@ -595,6 +597,21 @@ def llama_to_w8a16(state: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]
     for k, v in state.items():
         if _W8A16_LINEAR.match(k):
             out[k], out[k + "_scale"] = quant_weight_w8a16(v)
+        else:
+            out[k] = v
+    return out
+
+
+def llama_to_w4a16(state: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
+    """llama_to_w8a16's counterpart for a decoder built with quant="w4a16g128": every layer's wqkv / wo / w13 / w2 of the rank's
+    own shard becomes the packed codes plus `<name>_scale` (quantize.w4a16: quant_weight_w4a16, then pack_w4a16 -- w13 per
+    half).  The scale groups of a row-parallel shard are groups of its local K."""
+    from .quantize.w4a16 import pack_w4a16, quant_weight_w4a16
+
+    out = {}
+    for k, v in state.items():
+        if _W8A16_LINEAR.match(k):
+            out[k], out[k + "_scale"] = pack_w4a16(*quant_weight_w4a16(v), halves=2 if k.endswith("w13") else 1)
         else:
             out[k] = v
     return out

@@ -13,8 +13,10 @@
 //   weight_t, Scale          element type of W; the per-column scale of the epilogue (NoScale | RowScale, gemm_common.h)
 //   depth<NW, MT>()          ring depth for NW row groups per stage (2: plain, 4: gate + up) and MT token tiles
 //   Stage<MT, NW>            what a wave holds of one K step
+//   w_stride(K)              weight_t elements between two weight rows
 //   steps()                  K steps of a row
 //   w_off() / x_off()        the lane's element offset inside a weight row's / an activation row's step
+//   bind<NW>(scale, rows, n0) what the lane keeps of the launch's Scale for its own use (Int4Line: its group-scale rows)
 //   load(stage, wp, xp, s)   request step s
 //   mfma(stage, e, o, s)     e[r][mt], o[r][mt] += the step's product of row group r and token tile mt
 // Two bodies use it: stream_gemm (plain, gemm_epilogue_v2) and stream_gemm_silu (gate / up pairs, silu_reduce_store).  The
@@ -79,6 +81,9 @@ struct Bf16Line {
         s16x8 w[NW];
         s16x8 x[MT][2];
     };
+    static __device__ __forceinline__ int w_stride(int K) { return K; }
+    template <int NW>
+    __device__ __forceinline__ void bind(const NoScale&, int, int) {}
     int K, eoff, g8;
     __device__ __forceinline__ Bf16Line(int K_, int j, int g) : K(K_), eoff(((j & 1) * 4 + g) * 8), g8(g * 8) {}
     __device__ __forceinline__ int steps() const { return K >> 6; }
@@ -119,15 +124,17 @@ struct StreamLane {
     const typename L::weight_t* wp[NW];
     const bf16_t* xp[MT];
     f32x4 e[NW][MT], o[NW][MT];
-    __device__ __forceinline__ StreamLane(const bf16_t* X, const typename L::weight_t* W, int M, int rows, int K, int m_base)
+    __device__ __forceinline__ StreamLane(const bf16_t* X, const typename L::weight_t* W, const typename L::Scale& scale, int M,
+                                          int rows, int K, int m_base)
         : lane(threadIdx.x & 63), wave(__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)),  // wave-uniform: SGPR index math
           j(lane & 15), g(lane >> 4), n0(blockIdx.x * 16), line(K, j, g) {
         stream_share(line.steps(), wave, WK, first, last);
         // (unrolled in the source: around a loop LICM re-associates `base + row * K + lane offset` to hoist `base + lane
         // offset`, which the kernels this replaced did not have)
         static_for<NW>([&](auto r) {
-            wp[r] = W + (size_t)((r >> 1) * rows + min(n0 + (r & 1) * 8 + (j >> 1), rows - 1)) * K + line.w_off();
+            wp[r] = W + (size_t)((r >> 1) * rows + min(n0 + (r & 1) * 8 + (j >> 1), rows - 1)) * L::w_stride(K) + line.w_off();
         });
+        line.template bind<NW>(scale, rows, n0);
         static_for<MT>([&](auto mt) { xp[mt] = X + (size_t)min(m_base + mt * 16 + j, M - 1) * K + line.x_off(); });
 #pragma unroll
         for (int r = 0; r < NW; ++r)
@@ -150,7 +157,7 @@ __device__ __forceinline__ void stream_gemm(const bf16_t* __restrict__ X, const 
                                             typename L::Scale scale, void* __restrict__ out, int out_dt, int M, int N, int K,
                                             int m_base) {
     __shared__ float red[WK > 1 ? WK * MT * 256 : 1];
-    StreamLane<L, MT, 2, WK> ln(X, W, M, N, K, m_base);
+    StreamLane<L, MT, 2, WK> ln(X, W, scale, M, N, K, m_base);
     ln.template run<L::template depth<2, MT>(false)>();
     f32x4 acc[MT];
 #pragma unroll
@@ -227,7 +234,7 @@ __device__ __forceinline__ void stream_gemm_silu(const bf16_t* __restrict__ X, c
                                                  typename L::Scale scale, bf16_t* __restrict__ out, int M, int inter, int K,
                                                  int m_base) {
     __shared__ float red[WK > 1 ? WK * MT * 512 : 1];
-    StreamLane<L, MT, 4, WK> ln(X, W, M, inter, K, m_base);
+    StreamLane<L, MT, 4, WK> ln(X, W, scale, M, inter, K, m_base);
     ln.template run<L::template depth<4, MT>(false)>();
     f32x4 ag[MT], au[MT];
 #pragma unroll

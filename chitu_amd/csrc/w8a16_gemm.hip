@@ -56,6 +56,9 @@ struct Int8Line {
         i32x4 w[NW];
         s16x8 x[MT][4];
     };
+    static __device__ __forceinline__ int w_stride(int K) { return K; }
+    template <int NW>
+    __device__ __forceinline__ void bind(const RowScale&, int, int) {}
     int full_steps, tail, boff, hoff;  // hoff: the lane's half of a full line
     __device__ __forceinline__ Int8Line(int K, int j, int g) : full_steps(K >> 7), tail((K >> 6) & 1), boff(g * 16), hoff((j & 1) * 64) {}
     __device__ __forceinline__ int steps() const { return full_steps + tail; }

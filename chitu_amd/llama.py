@@ -42,7 +42,8 @@ class LlamaArgs:
     # Mistral-7B-v0.1: 4096); None: all of them.  Passed to the attention backend as window_size = (sliding_window - 1, 0).
     sliding_window: Optional[int] = None
     attn_softcap: float = 0.0  # > 0: scores are attn_softcap * tanh(score / attn_softcap) (the backend's softcap); 0.0: off
-    # "w8a16": wqkv, wo, w13 and w2 of every layer are int8 with one fp32 scale per output row (quantize/w8a16.py); None: bf16
+    # "w8a16": wqkv, wo, w13 and w2 of every layer are int8 with one fp32 scale per output row (quantize/w8a16.py);
+    # "w4a16g128": they are int4 codes with one fp32 scale per row and 128 input channels (quantize/w4a16.py); None: bf16
     quant: Optional[str] = None
 
     @property
@@ -51,13 +52,14 @@ class LlamaArgs:
 
 
 def check_quant_supported(quant, who: str, dense: bool = True) -> None:
-    """The `quant` field of the model args: None, or "w8a16" on the dense Llama-family decoders (Llama, Qwen2, Qwen3)."""
+    """The `quant` field of the model args: None, or "w8a16" / "w4a16g128" on the dense Llama-family decoders (Llama, Qwen2,
+    Qwen3, GLM-4).  The int4 name carries its group size: a bare "w4a16" is refused."""
     if quant is None:
         return
-    if quant != "w8a16":
-        raise ValueError(f"{who}: quant={quant!r} is not supported (None or 'w8a16')")
+    if quant not in ("w8a16", "w4a16g128"):
+        raise ValueError(f"{who}: quant={quant!r} is not supported (None, 'w8a16' or 'w4a16g128')")
     if not dense:
-        raise ValueError(f"{who}: quant='w8a16' covers the dense Llama-family decoders; this model's linears have their own formats")
+        raise ValueError(f"{who}: quant={quant!r} covers the dense Llama-family decoders; this model's linears have their own formats")
 
 
 def precompute_freqs_cis(head_dim: int, max_pos: int, theta: float):
@@ -73,9 +75,17 @@ def _param(*shape, device=None):
     return torch.nn.Parameter(torch.empty(*shape, dtype=torch.bfloat16, device=device), requires_grad=False)
 
 
-def _linear_weight(mod, name, n, k, quant, device):
-    """mod.<name>: the [n, k] weight of a linear -- bf16, or with quant "w8a16" int8 plus the fp32 row scales mod.<name>_scale."""
-    if quant == "w8a16":
+def _linear_weight(mod, name, n, k, quant, device, halves=1):
+    """mod.<name>: the [n, k] weight of a linear -- bf16, with quant "w8a16" int8 plus the fp32 row scales mod.<name>_scale, or
+    with quant "w4a16g128" packed uint8 [n, k / 2] plus the group scales in the kernel's order (quantize/w4a16.py::pack_w4a16;
+    halves = 2: w13, packed per half)."""
+    if quant == "w4a16g128":
+        if k % 128:
+            raise ValueError(f"quant='w4a16g128': {name} has a local K of {k}, not a multiple of the scale group (128)")
+        setattr(mod, name, torch.nn.Parameter(torch.empty(n, k // 2, dtype=torch.uint8, device=device), requires_grad=False))
+        setattr(mod, name + "_scale", torch.nn.Parameter(torch.empty(ops.w4a16_scale_shape(n, k, halves), dtype=torch.float32, device=device),
+                                                         requires_grad=False))
+    elif quant == "w8a16":
         setattr(mod, name, torch.nn.Parameter(torch.empty(n, k, dtype=torch.int8, device=device), requires_grad=False))
         setattr(mod, name + "_scale", torch.nn.Parameter(torch.empty(n, dtype=torch.float32, device=device), requires_grad=False))
     else:
@@ -83,10 +93,12 @@ def _linear_weight(mod, name, n, k, quant, device):
 
 
 def _linear(mod, name, x):
-    """x @ mod.<name>^T: the bf16 stream, or the W8A16 one when the weight is int8."""
+    """x @ mod.<name>^T: the bf16 stream, the W8A16 one when the weight is int8, the W4A16 one when it is packed uint8."""
     w = getattr(mod, name)
     if w.dtype == torch.int8:
         return ops.w8a16_linear(x, w, getattr(mod, name + "_scale"))
+    if w.dtype == torch.uint8:
+        return ops.w4a16_linear(x, w, getattr(mod, name + "_scale"))
     return ops.bf16_linear(x, w)
 
 
@@ -101,9 +113,9 @@ FUSE_NORM_MAX_BS = int(os.environ.get("CHITU_FUSE_NORM_MAX_BS", "2"))
 def _fuses_norm(x, pending, n_out, two_terms_ok: bool = False, weight=None) -> bool:
     """pending must be a plain [bs, dim] tensor: not None (first layer), not a partial whose all-reduce the norm launch
     itself performs (tensor_parallel.PendingAllReduce, the in-graph xGMI form).  two_terms_ok: also [bs, 2, dim] (a top-2 MoE's
-    un-summed outputs), for the prologue that takes them (ops.bf16_linear_add_norm).  weight: the matrix behind the norm; an int8
-    one (W8A16) has no prologue form and takes the norm launch and the linear separately."""
-    if weight is not None and weight.dtype == torch.int8:
+    un-summed outputs), for the prologue that takes them (ops.bf16_linear_add_norm).  weight: the matrix behind the norm; a
+    quantised one (W8A16 int8, W4A16 uint8) has no prologue form and takes the norm launch and the linear separately."""
+    if weight is not None and weight.dtype != torch.bfloat16:
         return False
     dims_ok = isinstance(pending, torch.Tensor) and (pending.dim() == 2 or (two_terms_ok and pending.dim() == 3 and pending.shape[1] == 2))
     return dims_ok and x.shape[0] <= FUSE_NORM_MAX_BS and ops.bf16_add_norm_fits(x.shape[0], n_out, x.shape[1])
@@ -269,12 +281,14 @@ class LlamaFeedForward(torch.nn.Module):
         t = tp.get_tp_size()
         self.inter = args.ffn_dim // t
         quant = getattr(args, "quant", None)
-        _linear_weight(self, "w13", 2 * self.inter, args.dim, quant, device)
+        _linear_weight(self, "w13", 2 * self.inter, args.dim, quant, device, halves=2)
         _linear_weight(self, "w2", args.dim, self.inter, quant, device)
 
     def forward(self, x):
         if self.w13.dtype == torch.int8:
             return _linear(self, "w2", ops.w8a16_linear_silu(x, self.w13, self.w13_scale))
+        if self.w13.dtype == torch.uint8:
+            return _linear(self, "w2", ops.w4a16_linear_silu(x, self.w13, self.w13_scale))
         return ops.bf16_linear(ops.bf16_linear_silu(x, self.w13), self.w2)
 
 

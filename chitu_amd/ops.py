@@ -1325,3 +1325,100 @@ def w8a16_linear_silu(x: torch.Tensor, q_w13: torch.Tensor, scale: torch.Tensor)
     check(_lib.lib().chitu_ext6_w8a16_gemm_silu(ptr(x), ptr(q_w13), ptr(scale), ptr(out), i64(M), i64(inter), i64(K), stream_ptr()),
           "w8a16_linear_silu")
     return out
+
+
+# ---------------------------------------------------------------- W4A16 g128 weight-only int4 linears (include/chitu_hip_ext9.h)
+def w4a16_tiled(M: int, n_rows: int, K: int) -> bool:
+    """True where a W4A16 linear over `n_rows` weight rows takes the widen + tiled bf16 GEMM form.  w8a16_tiled's rule: every M
+    it returns True for lies inside chitu_hip_bf16_gemm's own tiled rule, so the GEMM over the widened weights is the
+    compute-shaped one (tools/w4a16_ab.py --sweep measures it against the streaming form)."""
+    return w8a16_tiled(M, n_rows, K)
+
+
+def w4a16_plan(M: int, N: int, K: int, silu: bool = False):
+    """Mirror of the host's launch plan for w4a16_linear (N = output columns) / w4a16_linear_silu (N = inter): the form
+    ("stream" or "tiled") and, for the streaming form, one (MT, WK, ring depth) per 32-row launch -- the template arguments of
+    w4a16_gemm_kernel / w4a16_gemm_silu_kernel and Int4Line::depth (csrc/w4a16_gemm.hip).  A K step is 256 channels."""
+    if M <= 0:
+        return {"form": "none", "launches": []}
+    if w4a16_tiled(M, 2 * N if silu else N, K):
+        return {"form": "tiled", "launches": []}
+    tiles, steps, wk = (N + 15) // 16, (K + 255) // 256, 8
+    while wk > 1 and (wk > steps or tiles * wk > 4096):
+        wk >>= 1
+    launches = []
+    for mb in range(0, M, 32):
+        mt = 1 if M - mb <= 16 else 2
+        launches.append((mt, wk, (1 if mt == 2 else 2) if silu else (2 if mt == 2 else 4)))
+    return {"form": "stream", "launches": launches}
+
+
+def w4a16_scale_shape(n_rows: int, K: int, halves: int = 1):
+    """Shape of the kernel-order scales of a packed [n_rows, K / 2] matrix made of `halves` stacked matrices (2: w13)."""
+    return (halves * ((n_rows // halves + 1) // 2), (K + 255) // 256, 4)
+
+
+def _w4a16_check(x, packed, scales, halves=1):
+    require_cuda(x, packed, scales)
+    assert x.dtype == torch.bfloat16 and packed.dtype == torch.uint8 and scales.dtype == torch.float32
+    assert x.is_contiguous() and packed.is_contiguous() and scales.is_contiguous()
+    K = x.shape[-1]
+    assert K % 128 == 0 and packed.dim() == 2 and packed.shape[1] * 2 == K and packed.shape[0] % halves == 0
+    assert tuple(scales.shape) == w4a16_scale_shape(packed.shape[0], K, halves), (tuple(scales.shape), tuple(packed.shape))
+
+
+def w4a16_widen(packed: torch.Tensor, scales: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """W' = bf16(float(u - 8) * s) of one packed matrix, one fp32 multiply and one rounding: the weight operand of the tiled
+    bf16 GEMM.  out: bf16 [N, K] to fill (the workspace)."""
+    require_cuda(packed, scales)
+    assert packed.dtype == torch.uint8 and packed.dim() == 2 and packed.is_contiguous()
+    N, K = packed.shape[0], packed.shape[1] * 2
+    assert scales.dtype == torch.float32 and scales.is_contiguous() and tuple(scales.shape) == w4a16_scale_shape(N, K)
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=packed.device)
+    assert out.dtype == torch.bfloat16 and out.is_contiguous() and out.numel() == N * K
+    check(_lib.lib().chitu_ext9_w4a16_widen(ptr(packed), ptr(scales), ptr(out), i64(N), i64(K), stream_ptr()), "w4a16_widen")
+    return out
+
+
+def _w4a16_wide(packed, scales, halves):
+    """The matrix widened into the per-device workspace (sized by the largest linear seen); w13: one launch per half."""
+    rows, K = packed.shape[0], packed.shape[1] * 2
+    wide = workspace.get(rows * K * 2, packed.device, "w4a16_wide")[: rows * K * 2].view(torch.bfloat16).view(rows, K)
+    r, p = rows // halves, scales.shape[0] // halves
+    for h in range(halves):
+        w4a16_widen(packed[h * r : (h + 1) * r], scales[h * p : (h + 1) * p], wide[h * r : (h + 1) * r])
+    return wide
+
+
+def w4a16_linear(x: torch.Tensor, packed: torch.Tensor, scales: torch.Tensor, out_dtype=None) -> torch.Tensor:
+    """F.linear(x, dequant(packed, scales)) for int4 codes with one fp32 scale per row and 128 input channels
+    (quantize/w4a16.py::pack_w4a16 makes both tensors): out = round(sum_g s[n][g] * sum_{k in g} x[m][k] * (u[n][k] - 8)).
+    Decode batches stream the packed weights (a quarter of the bytes of bf16_linear); from w4a16_tiled's token count on the
+    weights are widened once to W' = bf16((u - 8) * s) and the result is bf16_linear(x, W'), bit for bit."""
+    _w4a16_check(x, packed, scales)
+    K = x.shape[-1]
+    M = x.numel() // K
+    N = packed.shape[0]
+    if w4a16_tiled(M, N, K):
+        return bf16_linear(x, _w4a16_wide(packed, scales, 1), out_dtype=out_dtype or torch.bfloat16)
+    out = torch.empty(*x.shape[:-1], N, dtype=out_dtype or torch.bfloat16, device=x.device)
+    check(_lib.lib().chitu_ext9_w4a16_gemm(ptr(x), ptr(packed), ptr(scales), ptr(out), float_dtype_code(out.dtype), i64(M), i64(N),
+                                           i64(K), stream_ptr()), "w4a16_linear")
+    return out
+
+
+def w4a16_linear_silu(x: torch.Tensor, packed13: torch.Tensor, scales13: torch.Tensor) -> torch.Tensor:
+    """silu(x w1^T) * (x w3^T) for packed13 = [w1; w3] (uint8 [2 inter, K / 2]; scales13: the scale pairs of w1, then of w3):
+    bf16_linear_silu's rounding chain on the scaled fp32 accumulators, one launch at decode batch sizes; from w4a16_tiled's
+    token count on bf16_linear_silu over the widened weights."""
+    _w4a16_check(x, packed13, scales13, halves=2)
+    K = x.shape[-1]
+    inter = packed13.shape[0] // 2
+    M = x.numel() // K
+    if w4a16_tiled(M, 2 * inter, K):
+        return bf16_linear_silu(x, _w4a16_wide(packed13, scales13, 2))
+    out = torch.empty(*x.shape[:-1], inter, dtype=torch.bfloat16, device=x.device)
+    check(_lib.lib().chitu_ext9_w4a16_gemm_silu(ptr(x), ptr(packed13), ptr(scales13), ptr(out), i64(M), i64(inter), i64(K),
+                                                stream_ptr()), "w4a16_linear_silu")
+    return out

@@ -1,11 +1,14 @@
 """Quantised linears on the decode path (reference: chitu/quantize/).  The W8A8 int8 path (`simple_w8a8`,
 quantizer.py:117-145) and the W8A16 weight-only int8 path (`w8a16`, quantizer.py:88-114,243-250) are on the MI355X hot
-path; AWQ / GPTQ / muxi variants are other formats backed by closed or third-party kernels and are out of scope
+path, and so is the symmetric group-128 int4 format of GPTQ checkpoints (`w4a16g128`, quantize/w4a16.py).  AWQ (asymmetric
+zero points), act-order GPTQ and the muxi variants are backed by closed or third-party kernels and are out of scope
 (SURVEY.md 2.2)."""
 
 from .w8a8 import W8A8Linear, quant_act, quant_weight, replace_with_simple_w8a8  # noqa: F401
 from .w8a16 import (WeightOnlyLinear, dequant_weight_w8a16, quant_weight_w8a16, quantize_w8a16_,  # noqa: F401
                     replace_with_w8a16)
+from .w4a16 import (W4A16Linear, dequant_weight_w4a16, from_gptq, pack_w4a16, quant_weight_w4a16, quantize_w4a16_,  # noqa: F401
+                    replace_with_w4a16, unpack_w4a16)
 
 
 def quant(model, method="simple_w8a8", **kwargs):
@@ -14,4 +17,6 @@ def quant(model, method="simple_w8a8", **kwargs):
         return replace_with_simple_w8a8(model, **kwargs)
     if method == "w8a16":
         return replace_with_w8a16(model, **kwargs)
+    if method == "w4a16g128":
+        return replace_with_w4a16(model, **kwargs)
     raise NotImplementedError(f"quant method {method!r} is not part of the MI355X decode path")
