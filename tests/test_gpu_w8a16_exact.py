@@ -5,7 +5,8 @@ prefill-sized case through the widen + tiled GEMM + scale_round form.  Every buf
 the output beyond [M, N], in the activations beyond M rows and in the scales beyond N, -128 in the weight rows beyond N.
 Nothing outside the extents may reach a result or be written.
 
-The SiLU entry's expectation restates the rounding chain on the CPU in fp32.  One step of it is not exactly specified on
+The SiLU entry's expectation restates the rounding chain on the CPU in fp32 (tests/silu_ref.py holds the candidate rule, shared
+with the W4A16 suite).  One step of it is not exactly specified on
 either side: exp(-g) goes through the device's expf and through the CPU's, each at most 1 ulp off (HIP's and glibc's
 documented bounds), so the two differ by at most 2 fp32 ulps = a factor within 1 -+ 2^-22.  The add and the divide behind it
 are correctly rounded and monotone on both sides, so the device's silu lies between the CPU chain evaluated at
@@ -17,6 +18,7 @@ import pytest
 import torch
 
 from tests import w8a16_ref as wr
+from tests.silu_ref import check_silu
 
 pytestmark = pytest.mark.gpu
 
@@ -75,28 +77,11 @@ def _assert_bits(got, want, what):
     assert bad.numel() == 0, (what, bad[:4].tolist(), got.flatten()[:4], want.flatten()[:4])
 
 
-def _silu_candidates(x, q13, s):
-    """(lo, hi): the two ends of the admissible bf16 outputs per element (equal except on a rounding boundary of silu's bf16
-    rounding): the fp32 chain of wr.expected_silu with exp(-g) moved by 2 fp32 ulps either way"""
+def _check_silu(got, x, q13, s, what):
+    """tests/silu_ref.py's check over this suite's accumulators: float32(acc) * s, exact integers times the row scale"""
     inter = q13.shape[0] // 2
     a = wr.acc_int(x, q13).to(torch.float32) * s.view(1, -1)
-    g, u = a[:, :inter].to(torch.bfloat16).float(), a[:, inter:].to(torch.bfloat16).float()
-    e = torch.exp(-g)
-    outs = []
-    for f in (1.0 - 2.0 ** -22, 1.0 + 2.0 ** -22):
-        sg = (g / (1.0 + e * torch.tensor(f, dtype=torch.float32))).to(torch.bfloat16).float()
-        outs.append((sg * u).to(torch.bfloat16))
-    return outs[0], outs[1]
-
-
-def _check_silu(got, x, q13, s, what):
-    lo, hi = _silu_candidates(x, q13, s)
-    want = wr.expected_silu(x, q13, s)
-    gb, lb, hb, wb = (t.contiguous().view(torch.int16) for t in (got, lo, hi, want))
-    free = lb != hb
-    assert bool(((gb == lb) | (gb == hb)).all()), (what, ((gb != lb) & (gb != hb)).nonzero()[:4].tolist())
-    assert bool((gb == wb)[~free].all()), what  # off a boundary the CPU's fp32 chain is the answer, bit for bit
-    return int(free.sum())
+    return check_silu(got, wr.expected_silu(x, q13, s), a[:, :inter], a[:, inter:], what)
 
 
 @pytest.mark.parametrize("kind", ["pow2", "quantiser"])
